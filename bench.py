@@ -26,14 +26,21 @@ the sets (the i8 layout prep is inside the step) and runs the batch.  Multi-GPU:
 batches are in flight on one GPU (--inflight).  The timed region runs with kernel
 timing off.
 
-Prints ONE JSON line on rank 0 with, besides the contract fields:
+A plain run sets up, warms up, times the `--steps` steps and prints ONE JSON line on rank 0 with the
+contract fields (metric, value, unit, higher_is_better, dtype, steps, warmup, ms_per_step, config).
+`--dump-outputs DIR` also writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32/float64; see dump_outputs), the inputs being seeded and so the same from run to run.
+
+`--full` adds, after the timed region, everything else the benchmark measures or checks:
   "roofline": the distance kernel's launch duration from HIP events in an isolated pass after the
       timed region (one batch at a time on one context, so an event pair brackets exactly that
       kernel; `rocprofv3 --kernel-trace --stats` of `--inflight 1` reproduces it), and
       the RANSAC bound kernel as an instruction roofline ("others");
   "cpu_baseline": oracle/ restatement on this host's cores, bounded sample (rank 0, N = 1);
   "parity": oracle records vs GPU records of sampled problems, summed over all ranks;
-  "ranks_seen".
+  "gather": the gathered records of the timed region summarised and compared with the rank's own;
+  c1img: the SIFT and single-scene latency figures; dataset: the detections against the golden run.
+(--cpu-sample, --cpu-rounds, --parity-sample, --iso-steps and --no-timing shape those parts.)
 `--dry-run` exercises the launcher, the C4 sharding and the gloo/RCCL record gather without a GPU.
 """
 from __future__ import annotations
@@ -94,6 +101,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c4", choices=["c1", "c1img", "c2", "c3", "c4", "c5", "dataset"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the isolated pass (rooflines, per-kernel times), the CPU "
+                         "baseline, the parity and gather checks and the latency figures (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-sample", type=int, default=6,
                     help="problems of the sequential CPU-baseline sample (1 warm-up + the median of the rest; "
                          "0: skip the CPU baseline)")
@@ -244,6 +256,34 @@ def host_cores() -> int:
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, integers as float64 (exact: all are int32),
+    floats as they are.  The configs' outputs are a few MB at most; a larger set is refused, not cut."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=v.dtype if v.dtype in (np.float32, np.float64) else np.float64)
+           for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes, over the {DUMP_LIMIT_BYTES} limit")
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+    log(f"wrote {', '.join(f'{k}{list(v.shape)}' for k, v in out.items())} to {path}")
+
+
+def record_arrays(recs):
+    """RESULT_DTYPE records (what match_batch and the record gather hand back) as one array per field."""
+    return {k: recs[k] for k in ("n_good", "n_inl", "status", "iters", "H", "det")}
+
+
+def detection_arrays(per_scene, names):
+    """Detections [((x, y, w, h), model name)] of each scene as rows (scene, model, x, y, w, h)."""
+    rows = [(s, names.index(n), *b) for s, dets in enumerate(per_scene) for b, n in dets]
+    return {"detections": np.asarray(rows, np.float64).reshape(-1, 6)}
 
 
 def _cmp_problem(o, r, det):
@@ -406,6 +446,27 @@ def run_c1img(args, rank, world, local):
         t = torch.tensor([el], dtype=torch.float64, device=torch.device("cuda", local))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    base = {"metric": "matches+homographies/sec (configs[0]: sugar_box model vs one test view, reference images, "
+                      "SIFT + match + RANSAC + boxes)",
+            "value": round(world * n_probs * args.steps / el, 3), "unit": "problems/s", "n_gpus": world,
+            "steps": args.steps, "warmup": n_warm + nf - 1, "ms_per_step": round(1e3 * el / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 SIFT (OpenCV order), i8-MFMA exact-int distances, fp64 DLT/LM, fp32 reprojection",
+            "data": f"reference images: 29 sugar_box model views + masks, test views {', '.join(my_ids)} (rank 0)",
+            "config": {"workload": f"c1img: detectObjects of one 640x480 scene against {len(names)} views x "
+                                   f"{len(SCALES)} scales = {n_probs} problems per step per GPU, the steps "
+                                   f"cycling through the rank's share of the {len(scenes)} test views",
+                       "problems_per_gpu": n_probs, "global_batch": world * n_probs, "parallelism": f"dp{world}",
+                       "scenes_in_flight": nf},
+            "scenes_per_s": round(world * args.steps / el, 3)}
+    if rank == 0 and args.dump_outputs:  # the last timed step's detections
+        dump_outputs(args.dump_outputs, detection_arrays([out_dets[(args.steps - 1) % nf] or []], [model.name]))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(base), flush=True)
+        for mm in ms:
+            mm.close()
+        return
     # SIFT of one 640x480 image alone (the step's dominant stage), timed separately
     ts = []
     for _ in range(5):
@@ -443,19 +504,7 @@ def run_c1img(args, rank, world, local):
     nt = np.array([len(k) for k in run.scene_kp], np.float64)
     knn_ops = float(2.0 * 128 * nq.sum() * nt.sum())  # every (view, scale) pair
     if rank == 0:
-        out = {"metric": "matches+homographies/sec (configs[0]: sugar_box model vs one test view, reference images, "
-                         "SIFT + match + RANSAC + boxes)",
-               "value": round(world * n_probs * args.steps / el, 3), "unit": "problems/s", "n_gpus": world,
-               "steps": args.steps, "warmup": n_warm + nf - 1, "ms_per_step": round(1e3 * el / args.steps, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32 SIFT (OpenCV order), i8-MFMA exact-int distances, fp64 DLT/LM, fp32 reprojection",
-               "data": f"reference images: 29 sugar_box model views + masks, test views {', '.join(my_ids)} (rank 0)",
-               "config": {"workload": f"c1img: detectObjects of one 640x480 scene against {len(names)} views x "
-                                      f"{len(SCALES)} scales = {n_probs} problems per step per GPU, the steps "
-                                      f"cycling through the rank's share of the {len(scenes)} test views",
-                          "problems_per_gpu": n_probs, "global_batch": world * n_probs, "parallelism": f"dp{world}",
-                          "scenes_in_flight": nf},
-               "scenes_per_s": round(world * args.steps / el, 3),
+        out = {**base,
                "sift_640x480_ms": round(1e3 * statistics.median(ts), 3),
                "single_scene_ms": round(scene_ms, 3),
                "single_scene_ms_range": [round(1e3 * min(lat), 3), round(1e3 * max(lat), 3)],
@@ -542,8 +591,8 @@ def run_dataset(args, rank, world, local):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     if rank == 0:
-        mism = [f"{f}/{s}" for (f, s), d in got.items()
-                if [[*b, n] for b, n in d] != exp["scenes"][f"{f}/{s[:-6]}"]["detections"]]
+        if args.dump_outputs:  # the last timed step's detections, scenes in the run's order
+            dump_outputs(args.dump_outputs, detection_arrays([got[(f, s)] for f, s, _ in scenes], objs))
         out = {"metric": "matches+homographies/sec (the reference's dataset: 3 models x 89 views vs its 30 test "
                          "images, SIFT + match + RANSAC + boxes + results files)",
                "value": round(len(scenes) * per_scene * args.steps / el, 3), "unit": "problems/s", "n_gpus": world,
@@ -557,10 +606,13 @@ def run_dataset(args, rank, world, local):
                           "problems_per_step": len(scenes) * per_scene, "scenes_rank0": len(mine),
                           "parallelism": f"dp{world}", "scenes_in_flight": nf},
                "scenes_per_s": round(len(scenes) * args.steps / el, 3),
-               "ms_per_scene": round(1e3 * el / (args.steps * len(scenes)), 3),
-               "parity": {"checked": len(got), "mismatch": len(mism), "first": mism[:3],
-                          "reference": "detections of the restatement's run of the same data "
-                                       "(tests/golden/dataset_expected.json; parity vs OpenCV unpinned)"}}
+               "ms_per_scene": round(1e3 * el / (args.steps * len(scenes)), 3)}
+        if args.full:
+            mism = [f"{f}/{s}" for (f, s), d in got.items()
+                    if [[*b, n] for b, n in d] != exp["scenes"][f"{f}/{s[:-6]}"]["detections"]]
+            out["parity"] = {"checked": len(got), "mismatch": len(mism), "first": mism[:3],
+                             "reference": "detections of the restatement's run of the same data "
+                                          "(tests/golden/dataset_expected.json; parity vs OpenCV unpinned)"}
         print(json.dumps(out), flush=True)
     for mm in ms:
         mm.close()
@@ -660,6 +712,51 @@ def kernel_rooflines(args, ds, res, iso, iso_step_ms, knn_only):
     return roof
 
 
+def _scene_chunk(a):
+    """Worker of bench_dataset: scenes `ids` of the batch.  Descriptor rows are integers in [0, 255]
+    held as float32 (synthetic.sift_like), so they travel back as uint8 without loss."""
+    from computervision_objectdetection_featurematching_amd.synthetic import make_dataset
+    n_models, n_scenes, nq, nt, n_plant, seed, ids = a
+    part = make_dataset(n_models, n_scenes, nq, nt, n_plant, seed=seed, scene_ids=ids)
+    return [d.astype(np.uint8) for d in part.scene_desc], part.scene_kp, part.H_true, part.plant_pos
+
+
+def parallel_config_dataset(name, seed, scene_ids=None, workers=None):
+    """synthetic.make_config_dataset(name, seed, scene_ids), the scenes generated by worker processes: a
+    scene is seeded by the seed and its id alone, so the data is the serial call's bit for bit (C4's
+    256 scenes take most of a minute on one core)."""
+    import multiprocessing as mp
+
+    from computervision_objectdetection_featurematching_amd.synthetic import CONFIGS, Dataset, make_config_dataset, make_dataset
+    cfg = CONFIGS[name]
+    ids = list(range(cfg["n_scenes"])) if scene_ids is None else [int(i) for i in scene_ids]
+    workers = min(host_cores() if workers is None else workers, len(ids))
+    if cfg.get("ragged") or workers < 2:
+        return make_config_dataset(name, seed=seed, scene_ids=scene_ids)
+    shape = (cfg["n_models"], cfg["n_scenes"], cfg["nq"], cfg["nt"], cfg["n_plant"], seed)
+    head = make_dataset(*shape[:5], seed=seed, scene_ids=[])  # the model sets
+    chunks = [ids[len(ids) * w // workers:len(ids) * (w + 1) // workers] for w in range(workers)]
+    with mp.get_context("fork").Pool(workers) as pool:
+        parts = pool.map(_scene_chunk, [(*shape, c) for c in chunks])
+    return Dataset(head.model_desc, head.model_kp, [d.astype(np.float32) for p in parts for d in p[0]],
+                   [k for p in parts for k in p[1]], np.concatenate([p[2] for p in parts], axis=1),
+                   np.concatenate([p[3] for p in parts], axis=1), head.n_plant, head.n_inl)
+
+
+def bench_dataset(args, rank, world):
+    """This rank's data of a synthetic config.  Sharded (C4): its contiguous block of the one global
+    batch's scenes, the same data at any N; --shard-of N (diagnostic, one process): rank 0's shard of an
+    N-rank run, i.e. the per-GPU workload of the strong-scaling point N (`value` is then this GPU's rate
+    on it).  Otherwise every rank has the same models and its own scenes (seeded by rank)."""
+    from computervision_objectdetection_featurematching_amd import shard
+    from computervision_objectdetection_featurematching_amd.synthetic import CONFIGS, SEED_BASE
+    cfg = CONFIGS[args.config]
+    if cfg.get("sharded"):
+        w_eff = args.shard_of if (args.shard_of > 0 and world == 1) else world
+        return parallel_config_dataset(args.config, SEED_BASE, shard.shard_range(cfg["n_scenes"], w_eff, rank))
+    return parallel_config_dataset(args.config, SEED_BASE + 1000 * rank)
+
+
 def args_max_iters(args) -> int:
     from computervision_objectdetection_featurematching_amd.synthetic import CONFIGS
     return int(CONFIGS[args.config]["max_iters"])
@@ -694,6 +791,8 @@ def main():
     if args.dry_run:
         return dry_run(args)
     rank, world, local = dist_env()
+    # the synthetic configs' data first: its worker processes run while this one has not opened the GPU
+    ds = None if args.config in ("c1img", "dataset") else bench_dataset(args, rank, world)
     import torch
     import torch.distributed as dist
     if args.dist_backend == "gloo":  # rehearsal: every rank on the visible GPU(s), round robin
@@ -714,14 +813,15 @@ def main():
             return run_c1img(args, rank, world, local)
         if args.config == "dataset":
             return run_dataset(args, rank, world, local)
-        return run_batches(args, rank, world, local)
+        return run_batches(args, rank, world, local, ds)
     finally:
         if dist.is_initialized():
             dist.destroy_process_group()
 
 
-def run_batches(args, rank, world, local):
-    """The synthetic configs (c1 surrogate, c2-c5): see the module docstring."""
+def run_batches(args, rank, world, local, ds):
+    """The synthetic configs (c1 surrogate, c2-c5) on this rank's data `ds` (bench_dataset): see the module
+    docstring."""
     import torch
     import torch.distributed as dist
     ranks_seen = dist.get_world_size() if dist.is_initialized() else 1
@@ -732,21 +832,17 @@ def run_batches(args, rank, world, local):
 
     from computervision_objectdetection_featurematching_amd import Matcher, build, default_params, shard
     from computervision_objectdetection_featurematching_amd._lib import RESULT_DTYPE
-    from computervision_objectdetection_featurematching_amd.synthetic import CONFIGS, SEED_BASE, make_config_dataset
+    from computervision_objectdetection_featurematching_amd.synthetic import CONFIGS
 
     build.build()
     cfg = CONFIGS[args.config]
     knn_only = bool(cfg.get("knn_only"))
     sharded = bool(cfg.get("sharded"))
-    if sharded:  # one global batch: this rank's contiguous block of its scenes (same data at any N)
-        # --shard-of N (diagnostic, one process): rank 0's shard of an N-rank run, i.e. the per-GPU
-        # workload of the strong-scaling point N; `value` is then this GPU's rate on it
+    if sharded:  # one global batch: this rank's contiguous block of its scenes (bench_dataset)
         w_eff = args.shard_of if (args.shard_of > 0 and world == 1) else world
         ids = shard.shard_range(cfg["n_scenes"], w_eff, rank)
-        ds = make_config_dataset(args.config, seed=SEED_BASE, scene_ids=ids)
         global_batch = cfg["n_scenes"] * cfg["n_models"] if w_eff == world else len(ids) * cfg["n_models"]
-    else:  # every rank: the same models, its own scenes (seeded by rank)
-        ds = make_config_dataset(args.config, seed=SEED_BASE + 1000 * rank)
+    else:
         global_batch = world * len(ds.problems)
     n_probs = len(ds.problems)
     # ranks hold shards differing by at most one scene: records are gathered at the largest size
@@ -827,6 +923,70 @@ def run_batches(args, rank, world, local):
         el = float(t.item())
     total = global_batch * args.steps
     value = total / el
+
+    def headline():
+        metric = {"c3": "matches+homographies/sec (10k x 10k SIFT, 50k RANSAC iters)",
+                  "c4": "matches+homographies/sec (10k x 10k SIFT, 50k RANSAC iters) at 1/2/4/8 GPUs",
+                  "c2": "matches+homographies/sec (2k x 2k SIFT, 2k RANSAC iters)",
+                  "c1": "matches+homographies/sec (C1 surrogate: 29 views x 5 scales, ragged 100-500 x 1k-4k, "
+                        "2k RANSAC iters)",
+                  "c5": "knnMatch(k=2) problems/sec (50k x 50k SIFT dense distance contraction)"}[args.config]
+        nq_all = np.array([d.shape[0] for d in ds.model_desc])
+        nt_all = np.array([d.shape[0] for d in ds.scene_desc])
+        if cfg.get("ragged"):
+            workload = (f"c1: {len(ds.model_desc)} model views (Nq {nq_all.min()}-{nq_all.max()}) x {len(ds.scene_desc)} "
+                        f"scene scales (Nt {nt_all.min()}-{nt_all.max()}) per GPU, maxIters {cfg['max_iters']}")
+        elif knn_only:
+            workload = f"c5: {cfg['nq']} x {cfg['nt']} descriptors, distance + top-2 only"
+        elif sharded:
+            workload = (f"c4: one global batch of {cfg['n_scenes']} scenes x {cfg['n_models']} model set, "
+                        f"{cfg['nq']}x{cfg['nt']} descriptors, maxIters {cfg['max_iters']}, scenes sharded over "
+                        f"{world} GPU(s) ({n_probs} on rank 0)")
+        else:
+            workload = (f"{args.config}: {cfg['n_models']} models x {cfg['n_scenes']} scenes per GPU, "
+                        f"{cfg['nq']}x{cfg['nt']} descriptors, maxIters {cfg['max_iters']}")
+        out = {
+            "metric": metric, "value": round(value, 3), "unit": "problems/s", "n_gpus": world,
+            "ranks_seen": ranks_seen, "steps": args.steps,
+            "warmup": n_warm, "ms_per_step": round(1e3 * el / args.steps, 3),
+            "host_enqueue_ms_per_step": round(1e3 * t_host / args.steps, 3), "higher_is_better": True,
+            "scaling": "strong" if sharded else "weak", "vs_baseline": None,
+            "dtype": "i8-MFMA exact-int distances (i32 acc)" + ("" if knn_only else
+                                                               ", fp64 DLT/Jacobi, fp32 reprojection"),
+            "data": "synthetic SIFT-like integer descriptors (seeded)" + ("" if knn_only else
+                                                                        ", planted geometric inliers"),
+            "config": {"workload": workload, "problems_per_gpu": n_probs, "global_batch": global_batch,
+                       "parallelism": f"dp{world}", "batches_in_flight": nf, "dist_backend": args.dist_backend,
+                       "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"])},
+        }
+        if sharded and args.shard_of > 0 and world == 1:
+            out["config"]["emulated_shard"] = (f"rank 0's shard of a {args.shard_of}-rank run ({n_probs} problems): "
+                                               f"per-GPU rate at that strong-scaling point, not a whole-job value")
+        if warm_note := ("" if n_warm == args.warmup else f"--warmup {args.warmup} raised to {n_warm}: every one of "
+                                                            f"the {nf} contexts runs once before the timed region"):
+            out["warmup_note"] = warm_note
+        if os.environ.get("MIM_BENCH_GATHER", "1") == "0":
+            out["diagnostic"] = "MIM_BENCH_GATHER=0: the per-step record gather left out (not a contract line)"
+        return out
+
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # what the last timed step handed its caller: the gathered records of every rank's problems
+        # (shards without their padding, so the global batch in scene order), C5: the top-2 table
+        k_last = (counter[0] - 1) % nf
+        if knn_only:
+            dump_outputs(args.dump_outputs, {"knn_idx": knn_idx[k_last].cpu().numpy(),
+                                             "knn_dist": knn_dist[k_last].cpu().numpy()})
+        else:
+            recs = shard.decode(gath[k_last] if gath[k_last] is not None else mine[k_last].view(1, -1))
+            per_rank = ([len(shard.shard_range(global_batch, world, r)) for r in range(recs.shape[0])] if sharded
+                        else [n_probs] * recs.shape[0])
+            dump_outputs(args.dump_outputs, record_arrays(np.concatenate([recs[r, :n] for r, n in enumerate(per_rank)])))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        for mm in matchers:
+            mm.close()
+        return
     # the timed region's records as gathered (all ranks): a cut-short RANSAC (RNG stream exhausted,
     # status 5) would have been counted as throughput; batch_results() re-runs such a batch, a device
     # copy cannot, so they are counted here and fail the parity check
@@ -905,46 +1065,7 @@ def run_batches(args, rank, world, local):
         dist.all_reduce(tot)  # every rank's parity sample and cut-short count
 
     if rank == 0:
-        metric = {"c3": "matches+homographies/sec (10k x 10k SIFT, 50k RANSAC iters)",
-                  "c4": "matches+homographies/sec (10k x 10k SIFT, 50k RANSAC iters) at 1/2/4/8 GPUs",
-                  "c2": "matches+homographies/sec (2k x 2k SIFT, 2k RANSAC iters)",
-                  "c1": "matches+homographies/sec (C1 surrogate: 29 views x 5 scales, ragged 100-500 x 1k-4k, "
-                        "2k RANSAC iters)",
-                  "c5": "knnMatch(k=2) problems/sec (50k x 50k SIFT dense distance contraction)"}[args.config]
-        nq_all = np.array([d.shape[0] for d in ds.model_desc])
-        nt_all = np.array([d.shape[0] for d in ds.scene_desc])
-        if cfg.get("ragged"):
-            workload = (f"c1: {len(ds.model_desc)} model views (Nq {nq_all.min()}-{nq_all.max()}) x {len(ds.scene_desc)} "
-                        f"scene scales (Nt {nt_all.min()}-{nt_all.max()}) per GPU, maxIters {cfg['max_iters']}")
-        elif knn_only:
-            workload = f"c5: {cfg['nq']} x {cfg['nt']} descriptors, distance + top-2 only"
-        elif sharded:
-            workload = (f"c4: one global batch of {cfg['n_scenes']} scenes x {cfg['n_models']} model set, "
-                        f"{cfg['nq']}x{cfg['nt']} descriptors, maxIters {cfg['max_iters']}, scenes sharded over "
-                        f"{world} GPU(s) ({n_probs} on rank 0)")
-        else:
-            workload = (f"{args.config}: {cfg['n_models']} models x {cfg['n_scenes']} scenes per GPU, "
-                        f"{cfg['nq']}x{cfg['nt']} descriptors, maxIters {cfg['max_iters']}")
-        out = {
-            "metric": metric, "value": round(value, 3), "unit": "problems/s", "n_gpus": world,
-            "ranks_seen": ranks_seen, "steps": args.steps,
-            "warmup": n_warm, "ms_per_step": round(1e3 * el / args.steps, 3),
-            "host_enqueue_ms_per_step": round(1e3 * t_host / args.steps, 3), "higher_is_better": True,
-            "scaling": "strong" if sharded else "weak", "vs_baseline": None,
-            "dtype": "i8-MFMA exact-int distances (i32 acc)" + ("" if knn_only else
-                                                               ", fp64 DLT/Jacobi, fp32 reprojection"),
-            "data": "synthetic SIFT-like integer descriptors (seeded)" + ("" if knn_only else
-                                                                        ", planted geometric inliers"),
-            "config": {"workload": workload, "problems_per_gpu": n_probs, "global_batch": global_batch,
-                       "parallelism": f"dp{world}", "batches_in_flight": nf, "dist_backend": args.dist_backend,
-                       "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"])},
-        }
-        if sharded and args.shard_of > 0 and world == 1:
-            out["config"]["emulated_shard"] = (f"rank 0's shard of a {args.shard_of}-rank run ({n_probs} problems): "
-                                               f"per-GPU rate at that strong-scaling point, not a whole-job value")
-        if warm_note := ("" if n_warm == args.warmup else f"--warmup {args.warmup} raised to {n_warm}: every one of "
-                                                            f"the {nf} contexts runs once before the timed region"):
-            out["warmup_note"] = warm_note
+        out = headline()
         if res is not None:
             out["accepted_problems_rank0"] = int((res["status"] == 0).sum())
         if roof:
@@ -960,8 +1081,6 @@ def run_batches(args, rank, world, local):
         if gather_check is not None:
             gather_check["ranks_own_row_differs"] = int(tot[3])  # summed over ranks
             out["gather"] = gather_check
-        if os.environ.get("MIM_BENCH_GATHER", "1") == "0":
-            out["diagnostic"] = "MIM_BENCH_GATHER=0: the per-step record gather left out (not a contract line)"
         print(json.dumps(out), flush=True)
     for mm in matchers:
         mm.close()

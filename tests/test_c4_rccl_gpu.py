@@ -25,7 +25,7 @@ def test_c4_full_batch_rccl_gather():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--config", "c4", "--steps", "2", "--warmup", "1",
            "--inflight", "2", "--cpu-sample", "0", "--parity-sample", "8", "--iso-steps", "1",
-           "--dist-backend", "nccl"]
+           "--dist-backend", "nccl", "--full"]  # --full: the gather and parity checks asserted below
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
