@@ -24,6 +24,7 @@ EXPORTS = [
     "mim_group_shard", "mim_group_create", "mim_group_destroy", "mim_group_size", "mim_group_uses_rccl",
     "mim_group_ctx", "mim_group_last_error", "mim_group_set_create", "mim_group_scene_batch_run",
     "mim_group_results",
+    "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_group_scene_images_run", "mim_group_scene_points",
 ]
 
 
@@ -59,6 +60,11 @@ class Problem(C.Structure):
 
 class HostSet(C.Structure):  # mim_host_set
     _fields_ = [("desc", C.c_void_p), ("kp_xy", C.c_void_p), ("n", C.c_int32)]
+
+
+class Image(C.Structure):  # mim_image
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("channels", C.c_int32),
+                ("step", C.c_int64)]
 
 
 RESULT_DTYPE = np.dtype([("n_good", np.int32), ("n_inl", np.int32), ("status", np.int32),
@@ -117,6 +123,8 @@ def load():
                                           C.POINTER(C.c_int32)]
     L.mim_sift_detect_compute_scales.argtypes = [vp, u8p, i32, i32, C.c_int64, i32, vp, i32, vp, f32p, vp]
     L.mim_sift_scales_sets.argtypes = [vp, u8p, i32, i32, C.c_int64, i32, vp, vp, vp, i32, vp]
+    L.mim_sift_scales_sets_image.argtypes = [vp, C.POINTER(Image), i32, vp, vp, vp, i32, vp]
+    L.mim_cvt_bgr2gray_u8.argtypes = [vp, u8p, i32, i32, C.c_int64, u8p]
     L.mim_resize_linear_u8.argtypes = [vp, u8p, i32, i32, C.c_int64, u8p, i32, i32, C.c_double, C.c_double]
     L.mim_default_box_params.argtypes = [C.POINTER(BoxParams)]
     L.mim_detect_boxes.argtypes = [f32p, i32, C.POINTER(BoxParams), C.POINTER(Rect), i32, C.POINTER(C.c_int32)]
@@ -132,8 +140,12 @@ def load():
     L.mim_group_set_create.argtypes = [vp, f32p, f32p, i32, i32, C.POINTER(C.c_int32)]
     L.mim_group_scene_batch_run.argtypes = [vp, i32, i32, C.POINTER(HostSet), i32, C.POINTER(Problem), C.POINTER(Params)]
     L.mim_group_results.argtypes = [vp, vp]
+    L.mim_group_scene_images_run.argtypes = [vp, i32, C.POINTER(Image), i32, f32p, i32, C.POINTER(Problem),
+                                             C.POINTER(Params)]
+    L.mim_group_scene_points.argtypes = [vp, i32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     for name in ("mim_group_shard", "mim_group_create", "mim_group_size", "mim_group_uses_rccl", "mim_group_set_create",
-                 "mim_group_scene_batch_run", "mim_group_results"):
+                 "mim_group_scene_batch_run", "mim_group_results", "mim_group_scene_images_run",
+                 "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8"):
         getattr(L, name).restype = C.c_int32
     for name in ("mim_ctx_create", "mim_ctx_set_stream", "mim_synchronize", "mim_set_create", "mim_sets_create", "mim_sets_clear",
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",

@@ -1031,20 +1031,21 @@ static mim_status scales_sets_register(mim_ctx* c, const mim::SiftDevOut* out, i
     return MIM_OK;
 }
 
-mim_status mim_sift_scales_sets(mim_ctx* c, const uint8_t* gray, int32_t rows, int32_t cols, int64_t step,
-                                int32_t n_scales, const float* scales, int32_t* set_ids, int32_t* n_kp, int32_t max_kp,
-                                mim_keypoint* kps) {
-    if (!c) return MIM_EINVAL;
-    if (!gray || !set_ids || !n_kp || !scales || n_scales <= 0 || n_scales > 8 || rows <= 0 || cols <= 0 ||
-        step < cols || max_kp < 0 || (max_kp > 0 && !kps))
+// mim_sift_scales_sets and mim_sift_scales_sets_image: the scene (channels 1 or 3, checked by the
+// callers) resized and described at every scale on the device, the scales registered as sets
+static mim_status sift_scales_sets_impl(mim_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int64_t step,
+                                        int32_t channels, int32_t n_scales, const float* scales, int32_t* set_ids,
+                                        int32_t* n_kp, int32_t max_kp, mim_keypoint* kps) {
+    if (!img || !set_ids || !n_kp || !scales || n_scales <= 0 || n_scales > 8 || rows <= 0 || cols <= 0 ||
+        step < (int64_t)cols * channels || max_kp < 0 || (max_kp > 0 && !kps))
         return fail(c, MIM_EINVAL, "sift_scales_sets: bad arguments");
     for (int i = 0; i < n_scales; ++i)
         if (!(scales[i] > 0)) return fail(c, MIM_EINVAL, "sift_scales_sets: scale %d is not > 0", i);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<mim::SiftDevOut> out(n_scales);
-    const int r = mim::sift_scales_device(c->sift_scales, c->stream, gray, rows, cols, step, n_scales, scales, out.data(),
-                                          c->err);
+    const int r = mim::sift_scales_device(c->sift_scales, c->stream, img, rows, cols, step, channels, n_scales, scales,
+                                          out.data(), c->err);
     if (r == -1) return MIM_EDEVICE;
     if (r == -3) return MIM_EINVAL;
     if (r == -4) return MIM_ELIMIT;
@@ -1075,6 +1076,43 @@ mim_status mim_sift_scales_sets(mim_ctx* c, const uint8_t* gray, int32_t rows, i
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (kps && total > max_kp) return fail(c, MIM_ERANGE, "sift_scales_sets: %lld keypoints, buffer holds %d", total, max_kp);
+    return MIM_OK;
+}
+
+mim_status mim_sift_scales_sets(mim_ctx* c, const uint8_t* gray, int32_t rows, int32_t cols, int64_t step,
+                                int32_t n_scales, const float* scales, int32_t* set_ids, int32_t* n_kp, int32_t max_kp,
+                                mim_keypoint* kps) {
+    if (!c) return MIM_EINVAL;
+    return sift_scales_sets_impl(c, gray, rows, cols, step, 1, n_scales, scales, set_ids, n_kp, max_kp, kps);
+}
+
+mim_status mim_sift_scales_sets_image(mim_ctx* c, const mim_image* scene, int32_t n_scales, const float* scales,
+                                      int32_t* set_ids, int32_t* n_kp, int32_t max_kp, mim_keypoint* kps) {
+    if (!c) return MIM_EINVAL;
+    if (!scene) return fail(c, MIM_EINVAL, "sift_scales_sets_image: null image");
+    if (scene->channels != 1 && scene->channels != 3)
+        return fail(c, MIM_EINVAL, "sift_scales_sets_image: %d channels (1: CV_8UC1, 3: CV_8UC3 BGR)", scene->channels);
+    if (scene->cols > 0 && scene->step < (int64_t)scene->cols * scene->channels)
+        return fail(c, MIM_EINVAL, "sift_scales_sets_image: step %lld < cols * channels = %lld", (long long)scene->step,
+                    (long long)scene->cols * scene->channels);
+    return sift_scales_sets_impl(c, scene->data, scene->rows, scene->cols, scene->step, scene->channels, n_scales,
+                                 scales, set_ids, n_kp, max_kp, kps);
+}
+
+mim_status mim_cvt_bgr2gray_u8(mim_ctx* c, const uint8_t* bgr, int32_t rows, int32_t cols, int64_t step,
+                               uint8_t* gray_out) {
+    if (!c) return MIM_EINVAL;
+    if (!bgr || !gray_out || rows <= 0 || cols <= 0)
+        return fail(c, MIM_EINVAL, "cvt_bgr2gray_u8: bad arguments");
+    if (step < (int64_t)cols * 3)
+        return fail(c, MIM_EINVAL, "cvt_bgr2gray_u8: step %lld < 3 * cols = %lld", (long long)step, (long long)cols * 3);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->sift) c->sift = mim::sift_ws_create();
+    const int r = mim::sift_bgr2gray_u8(c->sift, c->stream, bgr, rows, cols, step, gray_out, c->err);
+    if (r == -3) return MIM_EINVAL;
+    if (r == -4) return MIM_ELIMIT;
+    if (r != 0) return MIM_EDEVICE;
     return MIM_OK;
 }
 

@@ -10,6 +10,13 @@
 // records (padded to the largest range) on every device.  The query (model view) sets are replicated:
 // registered once per device, before the scene batches.  No descriptor crosses devices.
 //
+// A batch comes either as host descriptor sets (mim_group_scene_batch_run) or as the scene images
+// themselves, gray or BGR (mim_group_scene_images_run: Output.cpp:33 hands imread's result to
+// detectObjects): then each device also runs cvtColor, the resizes and SIFT of its own scenes
+// (mim_sift_scales_sets_image), and the inlier scene points of its problems (allUnfilteredScenePts,
+// TestsDetector.cpp:87-94) are fetched once per device into host memory of the group
+// (mim_group_scene_points); they never cross devices.
+//
 // Built only on the public C ABI of api.cpp (one ctx per device), plus HIP streams/events and RCCL.
 // A group whose device list repeats a device (two ctxs on one GPU: the test mode of a one-GPU box)
 // cannot hold an RCCL communicator (RCCL refuses two ranks on one device); it gathers with
@@ -39,6 +46,15 @@ struct mim_group {
     int n_scenes = 0, n_tmpl = 0, pad = 0;
     std::vector<int> first, count;
     bool pending = false;
+    // the last batch came from images (mim_group_scene_images_run): its scales and template, and the
+    // inlier points of every rank's problems in host memory once mim_group_scene_points has fetched them
+    bool images = false;
+    bool failed = false;  // an image batch failed after it had begun: no records, no points
+    std::vector<float> scales;
+    std::vector<mim_problem> tmpl;
+    bool pts_ready = false;
+    std::vector<std::vector<float>> pts;     // per rank: x, y of its problems' points
+    std::vector<std::vector<int64_t>> offs;  // per rank: count[r] * n_tmpl + 1 offsets into pts[r]
     std::string err;
 };
 
@@ -184,72 +200,8 @@ mim_status mim_group_set_create(mim_group* g, const float* desc, const float* kp
     return MIM_OK;
 }
 
-// One rank's part of a scene batch: its scenes' sets uploaded to its device, its problems enqueued,
-// its records copied into `send` (padded with zero records past its own).  Runs on its own host
-// thread per rank, so the uploads of the devices overlap; errors go to the rank's own string.
-static mim_status rank_run(mim_group* g, int r, int sets_per_scene, const mim_host_set* scene_sets, int n_tmpl,
-                           const mim_problem* tmpl, const mim_params* params, std::string& err) {
-    mim_ctx* c = g->ctx[r];
-    auto cfail = [&](mim_status s, const char* what) {
-        err = std::string("rank ") + std::to_string(r) + " (device " + std::to_string(g->dev[r]) + "): " + what + ": " +
-              mim_last_error(c);
-        return s;
-    };
-    auto hfail = [&](hipError_t e, const char* what) {
-        err = std::string("rank ") + std::to_string(r) + ": " + what + ": " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? (mim_status)MIM_ENOMEM : (mim_status)MIM_EDEVICE;
-    };
-    mim_status s = mim_sets_truncate(c, g->base_sets);
-    if (s != MIM_OK) return cfail(s, "sets_truncate");
-    const int ns = g->count[r] * sets_per_scene;
-    std::vector<const float*> desc(ns), kp(ns);
-    std::vector<int32_t> rows(ns);
-    for (int i = 0; i < ns; ++i) {
-        const mim_host_set& hs = scene_sets[(size_t)g->first[r] * sets_per_scene + i];
-        desc[i] = hs.desc;
-        kp[i] = hs.kp_xy;
-        rows[i] = hs.n;
-    }
-    int32_t first_id = 0;
-    if (ns > 0) {
-        s = mim_sets_create(c, ns, desc.data(), kp.data(), rows.data(), 128, 0, &first_id);
-        if (s != MIM_OK) return cfail(s, "sets_create");
-    }
-    std::vector<mim_problem> probs((size_t)g->count[r] * n_tmpl);
-    for (int j = 0; j < g->count[r]; ++j)
-        for (int k = 0; k < n_tmpl; ++k)
-            probs[(size_t)j * n_tmpl + k] = mim_problem{tmpl[k].query_set, first_id + j * sets_per_scene + tmpl[k].train_set};
-    s = mim_batch_run(c, probs.data(), (int32_t)probs.size(), params);
-    if (s != MIM_OK) return cfail(s, "batch_run");
-    hipError_t e = hipSetDevice(g->dev[r]);
-    if (e != hipSuccess) return hfail(e, "hipSetDevice");
-    hipStream_t st = (hipStream_t)mim_ctx_get_stream(c);
-    e = hipMemsetAsync(g->send[r], 0, sizeof(mim_result) * (size_t)g->pad, st);
-    if (e != hipSuccess) return hfail(e, "hipMemsetAsync");
-    s = mim_batch_results_copy(c, g->send[r], 1);
-    if (s != MIM_OK) return cfail(s, "batch_results_copy");
-    e = hipEventRecord(g->ev[r], st);
-    if (e != hipSuccess) return hfail(e, "hipEventRecord");
-    return MIM_OK;
-}
-
-mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t sets_per_scene,
-                                     const mim_host_set* scene_sets, int32_t n_tmpl, const mim_problem* tmpl,
-                                     const mim_params* params) {
-    if (!g) return MIM_EINVAL;
-    if (n_scenes < 0 || sets_per_scene < 1 || n_tmpl < 0 || !params || (n_scenes > 0 && !scene_sets) ||
-        (n_tmpl > 0 && !tmpl))
-        return gfail(g, MIM_EINVAL, "group_scene_batch_run: bad arguments");
-    for (int k = 0; k < n_tmpl; ++k)
-        if (tmpl[k].query_set < 0 || tmpl[k].query_set >= g->base_sets || tmpl[k].train_set < 0 ||
-            tmpl[k].train_set >= sets_per_scene)
-            return gfail(g, MIM_EINVAL, "group_scene_batch_run: template %d names set (%d, %d); %d replicated sets, %d "
-                                        "sets per scene", k, tmpl[k].query_set, tmpl[k].train_set, g->base_sets,
-                         sets_per_scene);
-    if (g->pending) {  // the previous batch's gather still reads `send`: finish it first
-        mim_status s = mim_group_results(g, nullptr);
-        if (s != MIM_OK) return s;
-    }
+// The split of a batch of n_scenes scenes over the ranks and the record buffers for it.
+static mim_status plan_batch(mim_group* g, int n_scenes, int n_tmpl) {
     const int W = (int)g->dev.size();
     g->first.assign(W, 0);
     g->count.assign(W, 0);
@@ -261,6 +213,7 @@ mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t set
     g->n_scenes = n_scenes;
     g->n_tmpl = n_tmpl;
     g->pad = std::max(1, maxc * n_tmpl);
+    g->pts_ready = false;
     if ((size_t)g->pad > g->cap) {
         release_buffers(g);
         for (int r = 0; r < W; ++r) {
@@ -270,21 +223,12 @@ mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t set
         }
         g->cap = (size_t)g->pad;
     }
-    std::vector<mim_status> st(W, MIM_OK);
-    std::vector<std::string> errs(W);
-    if (W == 1) {
-        st[0] = rank_run(g, 0, sets_per_scene, scene_sets, n_tmpl, tmpl, params, errs[0]);
-    } else {
-        std::vector<std::thread> th;
-        for (int r = 0; r < W; ++r)
-            th.emplace_back([&, r] { st[r] = rank_run(g, r, sets_per_scene, scene_sets, n_tmpl, tmpl, params, errs[r]); });
-        for (auto& t : th) t.join();
-    }
-    for (int r = 0; r < W; ++r)
-        if (st[r] != MIM_OK) {
-            g->err = errs[r];
-            return st[r];
-        }
+    return MIM_OK;
+}
+
+// Every rank's padded records (`send`, its event recorded) onto every rank (`recv`, rank-major).
+static mim_status gather_enqueue(mim_group* g) {
+    const int W = (int)g->dev.size();
     const size_t bytes = sizeof(mim_result) * (size_t)g->pad;
     if (!g->comm.empty()) {
         // one all-gather over xGMI: every device receives every rank's padded records, rank-major
@@ -312,8 +256,236 @@ mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t set
     return MIM_OK;
 }
 
+// A rank's errors go to its own string (the ranks run on their own host threads).
+static mim_status rank_cfail(mim_group* g, int r, mim_status s, const char* what, std::string& err) {
+    err = std::string("rank ") + std::to_string(r) + " (device " + std::to_string(g->dev[r]) + "): " + what + ": " +
+          mim_last_error(g->ctx[r]);
+    return s;
+}
+
+// The end of a rank's part of either kind of batch: its problems enqueued on its ctx, its records
+// copied into `send` (padded with zero records past its own), its event recorded.
+static mim_status rank_enqueue(mim_group* g, int r, const std::vector<mim_problem>& probs, const mim_params* params,
+                               std::string& err) {
+    mim_ctx* c = g->ctx[r];
+    auto cfail = [&](mim_status s, const char* what) { return rank_cfail(g, r, s, what, err); };
+    auto hfail = [&](hipError_t e, const char* what) {
+        err = std::string("rank ") + std::to_string(r) + ": " + what + ": " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? (mim_status)MIM_ENOMEM : (mim_status)MIM_EDEVICE;
+    };
+    mim_status s = mim_batch_run(c, probs.data(), (int32_t)probs.size(), params);
+    if (s != MIM_OK) return cfail(s, "batch_run");
+    hipError_t e = hipSetDevice(g->dev[r]);
+    if (e != hipSuccess) return hfail(e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)mim_ctx_get_stream(c);
+    e = hipMemsetAsync(g->send[r], 0, sizeof(mim_result) * (size_t)g->pad, st);
+    if (e != hipSuccess) return hfail(e, "hipMemsetAsync");
+    s = mim_batch_results_copy(c, g->send[r], 1);
+    if (s != MIM_OK) return cfail(s, "batch_results_copy");
+    e = hipEventRecord(g->ev[r], st);
+    if (e != hipSuccess) return hfail(e, "hipEventRecord");
+    return MIM_OK;
+}
+
+// One rank's part of a scene batch: its scenes' sets uploaded to its device, its problems enqueued,
+// its records copied into `send` (padded with zero records past its own).  Runs on its own host
+// thread per rank, so the uploads of the devices overlap; errors go to the rank's own string.
+static mim_status rank_run(mim_group* g, int r, int sets_per_scene, const mim_host_set* scene_sets, int n_tmpl,
+                           const mim_problem* tmpl, const mim_params* params, std::string& err) {
+    mim_ctx* c = g->ctx[r];
+    auto cfail = [&](mim_status s, const char* what) { return rank_cfail(g, r, s, what, err); };
+    mim_status s = mim_sets_truncate(c, g->base_sets);
+    if (s != MIM_OK) return cfail(s, "sets_truncate");
+    const int ns = g->count[r] * sets_per_scene;
+    std::vector<const float*> desc(ns), kp(ns);
+    std::vector<int32_t> rows(ns);
+    for (int i = 0; i < ns; ++i) {
+        const mim_host_set& hs = scene_sets[(size_t)g->first[r] * sets_per_scene + i];
+        desc[i] = hs.desc;
+        kp[i] = hs.kp_xy;
+        rows[i] = hs.n;
+    }
+    int32_t first_id = 0;
+    if (ns > 0) {
+        s = mim_sets_create(c, ns, desc.data(), kp.data(), rows.data(), 128, 0, &first_id);
+        if (s != MIM_OK) return cfail(s, "sets_create");
+    }
+    std::vector<mim_problem> probs((size_t)g->count[r] * n_tmpl);
+    for (int j = 0; j < g->count[r]; ++j)
+        for (int k = 0; k < n_tmpl; ++k)
+            probs[(size_t)j * n_tmpl + k] = mim_problem{tmpl[k].query_set, first_id + j * sets_per_scene + tmpl[k].train_set};
+    return rank_enqueue(g, r, probs, params, err);
+}
+
+mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t sets_per_scene,
+                                     const mim_host_set* scene_sets, int32_t n_tmpl, const mim_problem* tmpl,
+                                     const mim_params* params) {
+    if (!g) return MIM_EINVAL;
+    if (n_scenes < 0 || sets_per_scene < 1 || n_tmpl < 0 || !params || (n_scenes > 0 && !scene_sets) ||
+        (n_tmpl > 0 && !tmpl))
+        return gfail(g, MIM_EINVAL, "group_scene_batch_run: bad arguments");
+    for (int k = 0; k < n_tmpl; ++k)
+        if (tmpl[k].query_set < 0 || tmpl[k].query_set >= g->base_sets || tmpl[k].train_set < 0 ||
+            tmpl[k].train_set >= sets_per_scene)
+            return gfail(g, MIM_EINVAL, "group_scene_batch_run: template %d names set (%d, %d); %d replicated sets, %d "
+                                        "sets per scene", k, tmpl[k].query_set, tmpl[k].train_set, g->base_sets,
+                         sets_per_scene);
+    if (g->pending) {  // the previous batch's gather still reads `send`: finish it first
+        mim_status s = mim_group_results(g, nullptr);
+        if (s != MIM_OK) return s;
+    }
+    const int W = (int)g->dev.size();
+    mim_status ps = plan_batch(g, n_scenes, n_tmpl);
+    if (ps != MIM_OK) return ps;
+    g->images = false;
+    std::vector<mim_status> st(W, MIM_OK);
+    std::vector<std::string> errs(W);
+    if (W == 1) {
+        st[0] = rank_run(g, 0, sets_per_scene, scene_sets, n_tmpl, tmpl, params, errs[0]);
+    } else {
+        std::vector<std::thread> th;
+        for (int r = 0; r < W; ++r)
+            th.emplace_back([&, r] { st[r] = rank_run(g, r, sets_per_scene, scene_sets, n_tmpl, tmpl, params, errs[r]); });
+        for (auto& t : th) t.join();
+    }
+    for (int r = 0; r < W; ++r)
+        if (st[r] != MIM_OK) {
+            g->err = errs[r];
+            return st[r];
+        }
+    ps = gather_enqueue(g);
+    if (ps != MIM_OK) return ps;
+    g->failed = false;
+    return MIM_OK;
+}
+
+// One rank's part of an image batch: cvtColor + resize + SIFT of each of its scenes on its device, the
+// scales registered there as sets (mim_sift_scales_sets_image: one wait per scene, the counts), then
+// its problems and records (rank_enqueue).
+static mim_status rank_run_images(mim_group* g, int r, const mim_image* scenes, int n_scales, const mim_params* params,
+                                  std::string& err) {
+    mim_ctx* c = g->ctx[r];
+    auto cfail = [&](mim_status s, const char* what) { return rank_cfail(g, r, s, what, err); };
+    mim_status s = mim_sets_truncate(c, g->base_sets);
+    if (s != MIM_OK) return cfail(s, "sets_truncate");
+    const int n_tmpl = g->n_tmpl;
+    std::vector<mim_problem> probs((size_t)g->count[r] * n_tmpl);
+    std::vector<int32_t> ids(n_scales), n_kp(n_scales);
+    for (int j = 0; j < g->count[r]; ++j) {
+        s = mim_sift_scales_sets_image(c, &scenes[g->first[r] + j], n_scales, g->scales.data(), ids.data(), n_kp.data(),
+                                       0, nullptr);
+        if (s != MIM_OK) return cfail(s, ("scene " + std::to_string(g->first[r] + j) + ": sift_scales_sets_image").c_str());
+        for (int k = 0; k < n_tmpl; ++k)
+            probs[(size_t)j * n_tmpl + k] = mim_problem{g->tmpl[k].query_set, ids[g->tmpl[k].train_set]};
+    }
+    return rank_enqueue(g, r, probs, params, err);
+}
+
+// An image batch that failed after it had begun: what the ranks enqueued is waited for (the next
+// batch reuses `send`), and the group holds no batch until one succeeds.  The error text stays.
+static mim_status images_failed(mim_group* g, mim_status s) {
+    const std::string keep = g->err;
+    for (mim_ctx* c : g->ctx) (void)mim_synchronize(c);
+    g->pending = false;
+    g->failed = true;
+    g->pts_ready = false;
+    g->err = "group_scene_images_run failed: " + keep;
+    return s;
+}
+
+mim_status mim_group_scene_images_run(mim_group* g, int32_t n_scenes, const mim_image* scenes, int32_t n_scales,
+                                      const float* scales, int32_t n_tmpl, const mim_problem* tmpl,
+                                      const mim_params* params) {
+    if (!g) return MIM_EINVAL;
+    if (n_scenes < 0 || n_scales < 1 || n_scales > 8 || !scales || n_tmpl < 0 || !params || (n_scenes > 0 && !scenes) ||
+        (n_tmpl > 0 && !tmpl))
+        return gfail(g, MIM_EINVAL, "group_scene_images_run: bad arguments");
+    for (int k = 0; k < n_tmpl; ++k)
+        if (tmpl[k].query_set < 0 || tmpl[k].query_set >= g->base_sets || tmpl[k].train_set < 0 ||
+            tmpl[k].train_set >= n_scales)
+            return gfail(g, MIM_EINVAL, "group_scene_images_run: template %d names set (%d, %d); %d replicated sets, %d "
+                                        "scales", k, tmpl[k].query_set, tmpl[k].train_set, g->base_sets, n_scales);
+    if (g->pending) {  // the previous batch's gather still reads `send`: finish it first
+        mim_status s = mim_group_results(g, nullptr);
+        if (s != MIM_OK) return s;
+    }
+    const int W = (int)g->dev.size();
+    g->images = true;
+    g->scales.assign(scales, scales + n_scales);
+    g->tmpl.assign(tmpl, tmpl + n_tmpl);
+    mim_status ps = plan_batch(g, n_scenes, n_tmpl);
+    if (ps != MIM_OK) return images_failed(g, ps);
+    std::vector<mim_status> st(W, MIM_OK);
+    std::vector<std::string> errs(W);
+    if (W == 1) {
+        st[0] = rank_run_images(g, 0, scenes, n_scales, params, errs[0]);
+    } else {
+        std::vector<std::thread> th;
+        for (int r = 0; r < W; ++r)
+            th.emplace_back([&, r] { st[r] = rank_run_images(g, r, scenes, n_scales, params, errs[r]); });
+        for (auto& t : th) t.join();
+    }
+    for (int r = 0; r < W; ++r)
+        if (st[r] != MIM_OK) {
+            g->err = errs[r];
+            return images_failed(g, st[r]);
+        }
+    ps = gather_enqueue(g);
+    if (ps != MIM_OK) return images_failed(g, ps);
+    g->failed = false;
+    return MIM_OK;
+}
+
+// The inlier points of every rank's problems into the group's host memory (waits for the batch).
+static mim_status fetch_points(mim_group* g) {
+    const int W = (int)g->dev.size();
+    g->pts.assign(W, {});
+    g->offs.assign(W, {});
+    for (int r = 0; r < W; ++r) {
+        const size_t m = (size_t)g->count[r] * g->n_tmpl;
+        std::vector<float> sc(m);
+        for (size_t i = 0; i < m; ++i) sc[i] = g->scales[g->tmpl[i % g->n_tmpl].train_set];
+        g->offs[r].assign(m + 1, 0);
+        mim_status s = mim_batch_inlier_points(g->ctx[r], sc.data(), nullptr, 0, g->offs[r].data());
+        if (s != MIM_OK) return ctx_fail(g, r, s, "batch_inlier_points");
+        const int64_t total = g->offs[r][m];
+        g->pts[r].resize((size_t)total * 2);
+        if (total > 0) {
+            s = mim_batch_inlier_points(g->ctx[r], sc.data(), g->pts[r].data(), total, g->offs[r].data());
+            if (s != MIM_OK) return ctx_fail(g, r, s, "batch_inlier_points");
+        }
+    }
+    g->pts_ready = true;
+    return MIM_OK;
+}
+
+mim_status mim_group_scene_points(mim_group* g, int32_t scene, float* out_xy, int64_t cap, int64_t* offsets) {
+    if (!g) return MIM_EINVAL;
+    if (g->failed) return MIM_EINVAL;  // the text of the failed batch stays in mim_group_last_error
+    if (!g->images)
+        return gfail(g, MIM_EINVAL, "group_scene_points: the last batch was not an image batch "
+                                    "(mim_group_scene_images_run): its scales are not known");
+    if (!offsets || cap < 0 || scene < 0 || scene >= g->n_scenes)
+        return gfail(g, MIM_EINVAL, "group_scene_points: bad arguments (scene %d of %d)", scene, g->n_scenes);
+    if (!g->pts_ready) {
+        mim_status s = fetch_points(g);
+        if (s != MIM_OK) return s;
+    }
+    int r = 0;
+    while (scene >= g->first[r] + g->count[r]) ++r;
+    const int64_t* o = g->offs[r].data() + (size_t)(scene - g->first[r]) * g->n_tmpl;
+    for (int k = 0; k <= g->n_tmpl; ++k) offsets[k] = o[k] - o[0];
+    const int64_t total = offsets[g->n_tmpl];
+    if (!out_xy || total == 0) return MIM_OK;
+    if (total > cap)
+        return gfail(g, MIM_ERANGE, "group_scene_points: %lld points, buffer holds %lld", (long long)total, (long long)cap);
+    memcpy(out_xy, g->pts[r].data() + 2 * o[0], sizeof(float) * 2 * (size_t)total);
+    return MIM_OK;
+}
+
 mim_status mim_group_results(mim_group* g, mim_result* out) {
     if (!g) return MIM_EINVAL;
+    if (g->failed) return MIM_EINVAL;  // no batch: the text of the failed one stays in mim_group_last_error
     const int W = (int)g->dev.size();
     const size_t pad = (size_t)g->pad;
     std::vector<mim_result> all(pad * W);

@@ -187,8 +187,13 @@ struct SiftDevOut {
     const float* desc;
     int n;
 };
+// img: `channels` 1 (CV_8UC1) or 3 (CV_8UC3 in B, G, R order: converted to gray on the device first)
 int sift_scales_device(std::vector<SiftWs*>& ws, hipStream_t st, const uint8_t* img, int rows, int cols,
-                       long long step, int n_scales, const float* scales, SiftDevOut* out, std::string& err);
+                       long long step, int channels, int n_scales, const float* scales, SiftDevOut* out,
+                       std::string& err);
+// cvtColor(BGR2GRAY) of a CV_8UC3 image (row step `step` bytes) into the dense rows x cols plane `gray`
+int sift_bgr2gray_u8(SiftWs* w, hipStream_t st, const uint8_t* bgr, int rows, int cols, long long step, uint8_t* gray,
+                     std::string& err);
 // out[j]'s n rows and keypoint positions into ddesc[j] / dkp[j], j < n <= 8, one launch (0, -1 HIP error)
 int sift_copy_sets(const SiftDevOut* out, int n, float* const* ddesc, float2* const* dkp, hipStream_t st);
 }  // namespace mim

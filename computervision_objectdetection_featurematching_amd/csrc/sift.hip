@@ -167,6 +167,33 @@ __global__ void resize_u8_kernel(ResizeB A) {
     dst[(size_t)y * dcols + x] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// cvtColor(BGR2GRAY) of CV_8UC3 (preprocessImage, /root/reference/src/preprocessing.cpp:11): OpenCV's
+// 8-bit fixed-point weights (x 2^14, BT.601) with its rounding, gray = (R 4899 + G 9617 + B 1868 + 2^13)
+// >> 14.  The device copy is packed (no row padding), so the image is one run of n pixels: thread t
+// converts pixels 4t .. 4t + 3 from three dwords (bytes 12t .. 12t + 11, dword-aligned for every t)
+// into one dword; the last n % 4 pixels (cols % 4 != 0 with an odd row count, ...) go byte by byte.
+__device__ __forceinline__ uint32_t bgr_gray(uint32_t b, uint32_t g, uint32_t r) {
+    return (r * 4899u + g * 9617u + b * 1868u + (1u << 13)) >> 14;
+}
+
+__global__ __launch_bounds__(256) void bgr2gray_u8_kernel(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ gray,
+                                                          long long n) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long p = t * 4;
+    if (p >= n) return;
+    if (p + 4 <= n) {
+        const uint32_t* __restrict__ s = reinterpret_cast<const uint32_t*>(bgr) + t * 3;
+        const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];  // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+        const uint32_t g0 = bgr_gray(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
+        const uint32_t g1 = bgr_gray(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u);
+        const uint32_t g2 = bgr_gray((w1 >> 16) & 255u, w1 >> 24, w2 & 255u);
+        const uint32_t g3 = bgr_gray((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24);
+        reinterpret_cast<uint32_t*>(gray)[t] = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+    } else {
+        for (long long q = p; q < n; ++q) gray[q] = (uint8_t)bgr_gray(bgr[3 * q], bgr[3 * q + 1], bgr[3 * q + 2]);
+    }
+}
+
 struct Taps {
     float k[64];
     int n;
@@ -1340,6 +1367,7 @@ bool kp_greater(const mim_keypoint& a, const mim_keypoint& b) {  // KeypointGrea
 
 struct SiftWs {
     void* img = nullptr;   size_t img_cap = 0;
+    void* bgr = nullptr;   size_t bgr_cap = 0;  // a colour scene before bgr2gray_u8_kernel writes img
     void* pyr = nullptr;   size_t pyr_cap = 0;
     void* tmp = nullptr;   size_t tmp_cap = 0;
     void* aux = nullptr;   size_t aux_cap = 0;  // candidates, keypoints, counters, Pyr table
@@ -1373,7 +1401,7 @@ SiftWs* sift_ws_create() { return new SiftWs(); }
 
 void sift_ws_destroy(SiftWs* w) {
     if (!w) return;
-    for (void* p : {w->img, w->pyr, w->tmp, w->aux, w->desc, w->batch})
+    for (void* p : {w->img, w->bgr, w->pyr, w->tmp, w->aux, w->desc, w->batch})
         if (p) (void)hipFree(p);
     if (w->h_pyr) (void)hipHostFree(w->h_pyr);
     if (w->h_cnt) (void)hipHostFree(w->h_cnt);
@@ -1416,6 +1444,31 @@ static int stage_h2d(SiftWs* w, int slot, void* dst, const uint8_t* src, long lo
         for (int r = 0; r < rows; ++r) memcpy(S.p + (size_t)r * cols, src + (size_t)r * step, cols);
     SCHK(hipMemcpyAsync(dst, S.p, bytes, hipMemcpyHostToDevice, st));
     SCHK(hipEventRecord(S.ev, st));
+    return 0;
+}
+
+// The caller's 8-bit image, `channels` 1 (gray) or 3 (B, G, R interleaved), as the packed gray plane
+// w->img: the gray rows staged and copied as they are; a colour image staged as 3 cols bytes per row
+// into w->bgr and converted on the stream (bgr2gray_u8_kernel), so the stages after it read the same
+// plane either way.
+static int upload_gray(SiftWs* w, const uint8_t* img, int rows, int cols, long long step, int channels, hipStream_t st,
+                       std::string& err) {
+    const size_t n = (size_t)rows * cols;
+    SCHK(grow(w->img, w->img_cap, n));
+    if (channels == 1) return stage_h2d(w, 0, w->img, img, step, cols, rows, st, err);
+    if (channels != 3 || cols > INT_MAX / 3) {
+        err = "image: channels must be 1 or 3 (and 3 * cols < 2^31)";
+        return -3;
+    }
+    SCHK(grow(w->bgr, w->bgr_cap, 3 * n));
+    if (int r = stage_h2d(w, 0, w->bgr, img, step, 3 * cols, rows, st, err)) return r;
+    const long long nb = ((long long)(n + 3) / 4 + 255) / 256;
+    if (nb > INT_MAX) {
+        err = "image: too many pixels";
+        return -4;
+    }
+    bgr2gray_u8_kernel<<<(int)nb, 256, 0, st>>>((const uint8_t*)w->bgr, (uint8_t*)w->img, (long long)n);
+    SCHK(hipGetLastError());
     return 0;
 }
 
@@ -1881,16 +1934,15 @@ int sift_detect_compute(SiftWs* w, hipStream_t st, const uint8_t* img, int rows,
 
 // resize(scene, scaled, Size(), s, s, INTER_LINEAR) of every scale into its workspace, one launch
 static int sift_scale_images(std::vector<SiftWs*>& ws, hipStream_t st, const uint8_t* img, int rows, int cols,
-                             long long step, int n_scales, const float* scales, std::vector<SiftJob>& jobs,
-                             std::string& err) {
+                             long long step, int channels, int n_scales, const float* scales,
+                             std::vector<SiftJob>& jobs, std::string& err) {
     if (n_scales > kMaxImg) {
         err = "sift scales: more than 8 scales";
         return -3;
     }
     while ((int)ws.size() < n_scales + 1) ws.push_back(sift_ws_create());
     SiftWs* src = ws[n_scales];  // the scene itself, and the batch buffer
-    SCHK(grow(src->img, src->img_cap, (size_t)rows * cols));
-    if (int r = stage_h2d(src, 0, src->img, img, step, cols, rows, st, err)) return r;
+    if (int r = upload_gray(src, img, rows, cols, step, channels, st, err)) return r;
     jobs.assign(n_scales, SiftJob{});
     ResizeB A{};
     A.src = (const uint8_t*)src->img;
@@ -1933,7 +1985,7 @@ int sift_detect_compute_scales(std::vector<SiftWs*>& ws, hipStream_t st, const u
                                long long step, int n_scales, const float* scales, int max_kp, mim_keypoint* kps,
                                float* desc, int* n_out, std::string& err) {
     std::vector<SiftJob> jobs;
-    if (int r = sift_scale_images(ws, st, img, rows, cols, step, n_scales, scales, jobs, err)) return r;
+    if (int r = sift_scale_images(ws, st, img, rows, cols, step, 1, n_scales, scales, jobs, err)) return r;
     for (auto& J : jobs) J.cap = INT_MAX;  // the host path describes every keypoint: copies come below
     if (int r = sift_batch(jobs, ws[n_scales], st, err)) return r;
     int used = 0;
@@ -1956,11 +2008,13 @@ int sift_detect_compute_scales(std::vector<SiftWs*>& ws, hipStream_t st, const u
 }
 
 // The same on the device only: out[i] = scale i's keypoints / descriptors in the workspaces (valid until
-// the next SIFT call on them), one synchronisation (the counts)
+// the next SIFT call on them), one synchronisation (the counts).  img: `channels` 1 (gray) or 3 (BGR,
+// converted on the device first)
 int sift_scales_device(std::vector<SiftWs*>& ws, hipStream_t st, const uint8_t* img, int rows, int cols,
-                       long long step, int n_scales, const float* scales, SiftDevOut* out, std::string& err) {
+                       long long step, int channels, int n_scales, const float* scales, SiftDevOut* out,
+                       std::string& err) {
     std::vector<SiftJob> jobs;
-    if (int r = sift_scale_images(ws, st, img, rows, cols, step, n_scales, scales, jobs, err)) return r;
+    if (int r = sift_scale_images(ws, st, img, rows, cols, step, channels, n_scales, scales, jobs, err)) return r;
     for (auto& J : jobs) J.cap = INT_MAX;
     if (int r = sift_batch(jobs, ws[n_scales], st, err)) return r;
     for (int i = 0; i < n_scales; ++i) out[i] = SiftDevOut{jobs[i].out_kp, (const float*)jobs[i].w->desc, jobs[i].n};
@@ -2029,6 +2083,15 @@ int sift_resize_u8(SiftWs* w, hipStream_t st, const uint8_t* src, int rows, int 
     resize_u8_kernel<<<nb, 256, 0, st>>>(A);
     SCHK(hipGetLastError());
     SCHK(hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, st));
+    SCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// cvtColor(BGR2GRAY) alone: the colour rows up, the kernel, the dense gray plane back; synchronous
+int sift_bgr2gray_u8(SiftWs* w, hipStream_t st, const uint8_t* bgr, int rows, int cols, long long step, uint8_t* gray,
+                     std::string& err) {
+    if (int r = upload_gray(w, bgr, rows, cols, step, 3, st, err)) return r;
+    SCHK(hipMemcpyAsync(gray, w->img, (size_t)rows * cols, hipMemcpyDeviceToHost, st));
     SCHK(hipStreamSynchronize(st));
     return 0;
 }

@@ -5,6 +5,7 @@ Reference call sites (/root/reference/src/TestsDetector.cpp):
   :66-72   ratio test `m[0].distance < 0.9f * m[1].distance`           -> Matcher.ratio_filter
   :78      findHomography(objPts, scenePts, RANSAC, 5.0, inlierMask)   -> Matcher.find_homography
   :58-95   the per-view loop with its gates (:74, :79, :81, :84)       -> Matcher.match_batch
+  :33      preprocessImage: cvtColor(BGR2GRAY) (preprocessing.cpp:11)  -> Matcher.cvt_bgr2gray
   :102     resize(scene, scaled, Size(), s, s) (INTER_LINEAR)          -> Matcher.resize_linear
   :106     sift->detectAndCompute(scaled, noArray(), kps, desc)        -> Matcher.sift_detect_compute
   (ModelsDetector.cpp:75, the model views with their masks: the same call with a mask)
@@ -270,24 +271,46 @@ class Matcher:
             o += int(c)
         return out
 
+    def cvt_bgr2gray(self, bgr):
+        """cv::cvtColor(bgr, gray, COLOR_BGR2GRAY) of an H x W x 3 uint8 image (preprocessImage,
+        preprocessing.cpp:11) on the device: (R * 4899 + G * 9617 + B * 1868 + (1 << 13)) >> 14."""
+        b = np.asarray(bgr)
+        if b.dtype != np.uint8 or b.ndim != 3 or b.shape[2] != 3:
+            raise ValueError("cvt_bgr2gray: an H x W x 3 uint8 image (B, G, R) is required")
+        if b.strides[2] != 1 or b.strides[1] != 3 or b.strides[0] < 3 * b.shape[1]:
+            b = np.ascontiguousarray(b)
+        out = np.zeros(b.shape[:2], np.uint8)
+        self._check(self.L.mim_cvt_bgr2gray_u8(self._ctx, C.c_void_p(b.ctypes.data), b.shape[0], b.shape[1],
+                                               b.strides[0], C.c_void_p(out.ctypes.data)))
+        return out
+
     def sift_scales_to_sets(self, gray, scales, keypoints: bool = False, max_kp: int = 1 << 20):
         """resize + detectAndCompute at every scale (TestsDetector.cpp:99-107) with the descriptors left
-        on the device, each scale registered as a set (mim_sift_scales_sets).  Returns (set ids, n_kp
+        on the device, each scale registered as a set (mim_sift_scales_sets).  `gray` is an H x W uint8
+        image, or an H x W x 3 one in B, G, R order (what cv::imread gives), converted to gray on the
+        device first (preprocessing.cpp:11, mim_sift_scales_sets_image).  Returns (set ids, n_kp
         per scale, [keypoints per scale] or None); the sets' rows are what sift_detect_compute_scales
         returns, without the round trip through host memory.  With keypoints=True and more than max_kp
         keypoints in all, this call's sets are dropped and the call made again with room for all."""
         g = np.ascontiguousarray(gray, np.uint8)
-        if g.ndim != 2:
-            raise ValueError("sift_scales_to_sets: a single-channel image is required")
+        if g.ndim not in (2, 3):
+            raise ValueError("sift_scales_to_sets: an H x W (gray) or H x W x 3 (BGR) image is required")
         sc = np.ascontiguousarray(scales, np.float32).reshape(-1)
         ids = np.zeros(len(sc), np.int32)
         n = np.zeros(len(sc), np.int32)
         kps = np.zeros(max(max_kp, 1), KEYPOINT_DTYPE) if keypoints else None
         before = self.sets_info()[0]
-        st = self.L.mim_sift_scales_sets(
-            self._ctx, C.c_void_p(g.ctypes.data), g.shape[0], g.shape[1], g.strides[0], len(sc),
-            C.c_void_p(sc.ctypes.data), C.c_void_p(ids.ctypes.data), C.c_void_p(n.ctypes.data),
-            max_kp if keypoints else 0, C.c_void_p(kps.ctypes.data) if keypoints else None)
+        if g.ndim == 2:
+            st = self.L.mim_sift_scales_sets(
+                self._ctx, C.c_void_p(g.ctypes.data), g.shape[0], g.shape[1], g.strides[0], len(sc),
+                C.c_void_p(sc.ctypes.data), C.c_void_p(ids.ctypes.data), C.c_void_p(n.ctypes.data),
+                max_kp if keypoints else 0, C.c_void_p(kps.ctypes.data) if keypoints else None)
+        else:  # the channel count is the library's to check (MIM_EINVAL unless 3)
+            img = _lib.Image(C.c_void_p(g.ctypes.data), g.shape[0], g.shape[1], g.shape[2], g.strides[0])
+            st = self.L.mim_sift_scales_sets_image(
+                self._ctx, C.byref(img), len(sc), C.c_void_p(sc.ctypes.data), C.c_void_p(ids.ctypes.data),
+                C.c_void_p(n.ctypes.data), max_kp if keypoints else 0,
+                C.c_void_p(kps.ctypes.data) if keypoints else None)
         # the context's set count, whatever happened (MIM_ERANGE for a short host keypoint buffer comes
         # after the sets were registered)
         self._n_sets = self.sets_info()[0]

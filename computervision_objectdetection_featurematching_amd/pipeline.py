@@ -9,9 +9,10 @@ Mirrors (names, argument meaning, outputs):
 Every compute stage runs in libmim: resize and SIFT on the GPU (mim_resize_linear_u8,
 mim_sift_detect_compute), the (model, scale, view) problems as ONE device batch (knnMatch k=2 + ratio
 + findHomography RANSAC + gates, mim_batch_run), the boxes in the library's host stage
-(mim_detect_boxes = include/mim_detect.hpp).  Images are CV_8UC1 arrays: the grayscale conversion of
-preprocessImage (preprocessing.cpp:11) is the caller's (cv::imread(..., IMREAD_GRAYSCALE) or
-cvtColor), as is file decoding.
+(mim_detect_boxes = include/mim_detect.hpp).  A scene is a CV_8UC1 array, or a CV_8UC3 one in B, G, R
+order as cv::imread gives it: the grayscale conversion of preprocessImage (preprocessing.cpp:11) then
+runs on the GPU too (mim_sift_scales_sets_image), before the resizes.  Model views are CV_8UC1 (a
+colour view goes through Matcher.cvt_bgr2gray first); file decoding is the caller's.
 
 Differences from the reference, all without effect on the result:
   - the scene is resized and SIFT-described once per scale, not once per (model, scale)
@@ -123,7 +124,8 @@ class SceneRun:
 def detect_objects(matcher: Matcher, scene_gray, models: list[ObjectModel], scales=SCALES, params=None,
                    box_params: BoxParams | None = None, keep: bool = False, keep_descriptors: bool = False,
                    stage_ms: dict | None = None):
-    """detectObjects(scene, models, detector) (TestsDetector.cpp:32-251) on a grayscale scene.
+    """detectObjects(scene, models, detector) (TestsDetector.cpp:32-251) on a grayscale (H x W) or
+    colour (H x W x 3, B, G, R) uint8 scene.
 
     Returns [((x, y, w, h), name)], or the SceneRun when keep=True (its scene_desc only with
     keep_descriptors: the scene's descriptors never leave the device on the detection path; for the

@@ -235,6 +235,31 @@ mim_status mim_sift_scales_sets(struct mim_ctx* ctx, const uint8_t* gray, int32_
                                 int32_t n_scales, const float* scales, int32_t* set_ids, int32_t* n_kp, int32_t max_kp,
                                 mim_keypoint* kps);
 
+/* A host image as the reference holds its scenes (cv::Mat from imread, Output.cpp:33): rows x cols
+ * pixels of `channels` bytes, channels = 1 (CV_8UC1) or 3 (CV_8UC3 in B, G, R order), row stride `step`
+ * bytes >= cols * channels. */
+typedef struct {
+    const uint8_t* data;
+    int32_t rows, cols, channels;
+    int64_t step;
+} mim_image;
+
+/* mim_sift_scales_sets from the scene as it was read: channels == 1 is mim_sift_scales_sets(scene->data,
+ * ...) itself; channels == 3 first does preprocessImage's cvtColor(scene, gray, COLOR_BGR2GRAY)
+ * (preprocessing.cpp:11, the first line of detectObjects, TestsDetector.cpp:33) on the device: the
+ * colour rows uploaded once, converted on the ctx stream into the plane the resizes read.  Everything
+ * else (sets, counts, kps, statuses, synchronisations) as mim_sift_scales_sets.  Any other channel
+ * count, or step < cols * channels: MIM_EINVAL. */
+mim_status mim_sift_scales_sets_image(struct mim_ctx* ctx, const mim_image* scene, int32_t n_scales,
+                                      const float* scales, int32_t* set_ids, int32_t* n_kp, int32_t max_kp,
+                                      mim_keypoint* kps);
+
+/* cv::cvtColor(bgr, gray, COLOR_BGR2GRAY) of a CV_8UC3 image (preprocessing.cpp:11): OpenCV's 8-bit
+ * fixed-point form, gray = (R * 4899 + G * 9617 + B * 1868 + (1 << 13)) >> 14.  bgr stride `step` bytes
+ * (>= 3 * cols), gray_out dense rows x cols.  Synchronous. */
+mim_status mim_cvt_bgr2gray_u8(struct mim_ctx* ctx, const uint8_t* bgr, int32_t rows, int32_t cols, int64_t step,
+                               uint8_t* gray_out);
+
 /* cv::resize(src, dst, dsize, fx, fy, INTER_LINEAR) of a CV_8UC1 image (TestsDetector.cpp:102, the
  * scene scales).  fx, fy > 0: resize(src, dst, Size(), fx, fy) — the caller passes
  * drows = cvRound(rows * fy), dcols = cvRound(cols * fx) and OpenCV's coefficients use 1/fx, 1/fy;
@@ -309,6 +334,29 @@ mim_status mim_group_scene_batch_run(mim_group* g, int32_t n_scenes, int32_t set
  * buffer) to `out` (NULL: wait only).  A device whose problems ran out of RNG draws grows its stream
  * and re-runs its share first, as mim_batch_results. */
 mim_status mim_group_results(mim_group* g, mim_result* out);
+
+/* The same batch from the scene images themselves (processAllTestImages hands each imread result to
+ * detectObjects, Output.cpp:33-41): scenes[0 .. n_scenes) are host images, gray or BGR, of any sizes.
+ * Each device runs mim_sift_scales_sets_image on its own scenes (cvtColor, the n_scales <= 8 resizes
+ * and SIFT on that device, TestsDetector.cpp:33,99-107: n_scales sets per scene, never in host
+ * memory), then its problems as one mim_batch_run; tmpl[k].train_set is a scale index
+ * 0 .. n_scales - 1.  Records and gather as mim_group_scene_batch_run; the images are read before the
+ * call returns.  Unlike the descriptor-set entry it waits once per scene on each device (the SIFT
+ * counts).  If it fails after it has started, the group holds no batch: mim_group_results and
+ * mim_group_scene_points return an error (text in mim_group_last_error) until a batch succeeds. */
+mim_status mim_group_scene_images_run(mim_group* g, int32_t n_scenes, const mim_image* scenes, int32_t n_scales,
+                                      const float* scales, int32_t n_tmpl, const mim_problem* tmpl,
+                                      const mim_params* params);
+/* allUnfilteredScenePts (TestsDetector.cpp:87-94) of scene `scene` of the last image batch: for every
+ * accepted template problem in template order, the scene keypoints of its RANSAC inliers in mask
+ * order, each divided by scales[tmpl[k].train_set] when that is not 1.0f (scalePoints, :48-55).
+ * offsets (n_tmpl + 1 entries): template k's points are out_xy[2 offsets[k] .. 2 offsets[k + 1]).
+ * out_xy NULL: offsets only; offsets[n_tmpl] > cap: MIM_ERANGE (offsets valid, nothing copied).  The
+ * first call after a batch waits for it and runs mim_batch_inlier_points once on every device (which
+ * re-runs a share cut short by the RNG stream); the points stay in host memory of the group, and
+ * later calls are slices of it.  They never cross devices.  MIM_EINVAL after
+ * mim_group_scene_batch_run: the group does not know that batch's scales. */
+mim_status mim_group_scene_points(mim_group* g, int32_t scene, float* out_xy, int64_t cap, int64_t* offsets);
 
 /* ---- introspection for benches / profiles ----------------------------------------------------- */
 /* Per-kernel device time (ms) summed over the batches since the last result fetch, measured with

@@ -123,6 +123,20 @@ class Detector {
         run_sets(models, ids, scales, out);
     }
 
+    // detect_scene_gray from the scene as imread gives it (Output.cpp:33): a CV_8UC3 image (B, G, R) is
+    // converted on the device first (preprocessImage's cvtColor, preprocessing.cpp:11), a CV_8UC1 image
+    // is detect_scene_gray itself (mim_sift_scales_sets_image).
+    void detect_scene_image(const std::vector<const ModelViews*>& models, const mim_image& scene,
+                            const std::vector<float>& scales, std::vector<std::vector<Point2f>>& out) {
+        out.assign(models.size(), {});
+        register_models(models);
+        std::vector<int32_t> ids(scales.size()), n(scales.size());
+        check(mim_sift_scales_sets_image(ctx_, &scene, (int32_t)scales.size(), scales.data(), ids.data(), n.data(), 0,
+                                         nullptr),
+              "mim_sift_scales_sets_image", ctx_);
+        run_sets(models, ids, scales, out);
+    }
+
     void detect_scene(const std::vector<const ModelViews*>& models, const std::vector<ScaledScene>& scales,
                       std::vector<std::vector<Point2f>>& out) {
         out.assign(models.size(), {});
@@ -303,6 +317,92 @@ class Detector {
     std::vector<std::vector<int32_t>> reg_ids_;
     int32_t reg_n_ = -1;
     int64_t reg_gen_ = -1;  // the ctx's sets generation after this Detector's last clear/truncate
+};
+
+// processAllTestImages' scene loop (Output.cpp:23-57) over several GPUs of one node: a mim_group whose
+// devices each take a contiguous share of a batch of scene images (gray or BGR), run cvtColor, the
+// resizes, SIFT and every (model, scale, view) problem of their scenes, and keep their inlier points;
+// the records are gathered on every device.  out[scene][model] = that model's allUnfilteredScenePts,
+// as Detector::detect_scene_image gives for the scene alone.
+class GroupDetector {
+   public:
+    explicit GroupDetector(const std::vector<int>& devices) {
+        std::vector<int32_t> d(devices.begin(), devices.end());
+        const mim_status s = mim_group_create(d.data(), (int32_t)d.size(), &g_);
+        if (s != MIM_OK) throw Error(s, "mim_group_create: failed");
+        mim_default_params(&params_);
+    }
+    ~GroupDetector() { mim_group_destroy(g_); }
+    GroupDetector(const GroupDetector&) = delete;
+    GroupDetector& operator=(const GroupDetector&) = delete;
+
+    mim_params& params() { return params_; }
+    mim_group* group() { return g_; }
+
+    // Registers every view of every model on every device (mim_group_set_create).  The group's sets are
+    // only ever appended to, so call it once, with all the models.
+    void set_models(const std::vector<const ModelViews*>& models) {
+        view_ids_.assign(models.size(), {});
+        for (size_t m = 0; m < models.size(); ++m)
+            for (const View& v : models[m]->views) {
+                int32_t id = -1;
+                check(mim_group_set_create(g_, v.descriptors.data(), v.keypoints.empty() ? nullptr : &v.keypoints[0].x,
+                                           v.size(), 128, &id),
+                      "mim_group_set_create");
+                view_ids_[m].push_back(id);
+            }
+    }
+
+    // One batch over all the scenes.  Problem order within a scene: model outer, scale, view inner
+    // (Detector::run_sets), so a model's points are one slice of the scene's.
+    void detect_scenes(const std::vector<mim_image>& scenes, const std::vector<float>& scales,
+                       std::vector<std::vector<std::vector<Point2f>>>& out) {
+        std::vector<mim_problem> tmpl;
+        std::vector<size_t> model_end;  // templates of models 0 .. m
+        for (size_t m = 0; m < view_ids_.size(); ++m) {
+            for (size_t s = 0; s < scales.size(); ++s)
+                for (int32_t id : view_ids_[m]) tmpl.push_back({id, (int32_t)s});
+            model_end.push_back(tmpl.size());
+        }
+        n_tmpl_ = tmpl.size();
+        results_.clear();
+        check(mim_group_scene_images_run(g_, (int32_t)scenes.size(), scenes.data(), (int32_t)scales.size(),
+                                         scales.data(), (int32_t)tmpl.size(), tmpl.data(), &params_),
+              "mim_group_scene_images_run");
+        results_.assign(scenes.size() * tmpl.size(), mim_result{});
+        check(mim_group_results(g_, results_.data()), "mim_group_results");
+        out.assign(scenes.size(), std::vector<std::vector<Point2f>>(view_ids_.size()));
+        std::vector<int64_t> offs(tmpl.size() + 1);
+        std::vector<Point2f> pts;
+        for (size_t i = 0; i < scenes.size(); ++i) {
+            check(mim_group_scene_points(g_, (int32_t)i, nullptr, 0, offs.data()), "mim_group_scene_points");
+            pts.resize((size_t)offs.back());
+            if (!pts.empty())
+                check(mim_group_scene_points(g_, (int32_t)i, &pts[0].x, offs.back(), offs.data()),
+                      "mim_group_scene_points");
+            size_t t0 = 0;
+            for (size_t m = 0; m < view_ids_.size(); ++m) {
+                out[i][m].assign(pts.begin() + offs[t0], pts.begin() + offs[model_end[m]]);
+                t0 = model_end[m];
+            }
+        }
+    }
+
+    // The records of the last detect_scenes, scene-major: scene i's are [i * n, (i + 1) * n), n =
+    // templates_per_scene(), in the problem order above.
+    const std::vector<mim_result>& last_results() const { return results_; }
+    size_t templates_per_scene() const { return n_tmpl_; }
+
+   private:
+    void check(mim_status s, const char* what) {
+        if (s != MIM_OK) throw Error(s, std::string(what) + ": " + mim_group_last_error(g_));
+    }
+
+    mim_group* g_ = nullptr;
+    mim_params params_;
+    std::vector<std::vector<int32_t>> view_ids_;
+    std::vector<mim_result> results_;
+    size_t n_tmpl_ = 0;
 };
 
 }  // namespace mim
