@@ -25,6 +25,7 @@ EXPORTS = [
     "mim_group_ctx", "mim_group_last_error", "mim_group_set_create", "mim_group_scene_batch_run",
     "mim_group_results",
     "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_group_scene_images_run", "mim_group_scene_points",
+    "mim_set_create_bin", "mim_knn2_hamming",
 ]
 
 
@@ -98,6 +99,8 @@ def load():
     L.mim_ctx_get_stream.restype = vp
     L.mim_synchronize.argtypes = [vp]
     L.mim_set_create.argtypes = [vp, f32p, f32p, i32, i32, i32, C.POINTER(C.c_int32)]
+    L.mim_set_create_bin.argtypes = [vp, u8p, C.c_int64, f32p, i32, i32, i32, C.POINTER(C.c_int32)]
+    L.mim_knn2_hamming.argtypes = [vp, u8p, i32, u8p, i32, i32, i32p, f32p]
     L.mim_sets_create.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), i32p, i32, i32, C.POINTER(C.c_int32)]
     L.mim_sets_clear.argtypes = [vp]
     L.mim_sets_truncate.argtypes = [vp, i32]
@@ -145,7 +148,8 @@ def load():
     L.mim_group_scene_points.argtypes = [vp, i32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     for name in ("mim_group_shard", "mim_group_create", "mim_group_size", "mim_group_uses_rccl", "mim_group_set_create",
                  "mim_group_scene_batch_run", "mim_group_results", "mim_group_scene_images_run",
-                 "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8"):
+                 "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_set_create_bin",
+                 "mim_knn2_hamming"):
         getattr(L, name).restype = C.c_int32
     for name in ("mim_ctx_create", "mim_ctx_set_stream", "mim_synchronize", "mim_set_create", "mim_sets_create", "mim_sets_clear",
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",

@@ -27,6 +27,7 @@ void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStrea
 void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const int* seg_start, int n_blocks, Top2* parts,
                 int* dyn_ctr, hipStream_t st);
 int knn_blocks_per_cu();
+void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
 void launch_ratio(const ProbDev* probs, int n_probs, const Top2* parts, float ratio, int32_t* good_q,
                   int32_t* good_t, float4* pts, int* n_good, int32_t* knn_idx, float* knn_dist,
                   hipStream_t st);
@@ -106,6 +107,8 @@ struct Arena {
 struct SetRec {
     SetDev d;
     Arena::Mark mark;  // the arena before the set's storage (mim_sets_truncate)
+    int bin_pad = 0;   // binary set: bytes per padded row (16, 32 or 64); 0: a float set
+    int bin_width = 0; // binary set: the caller's bytes per row
 };
 
 // Pinned staging for the per-batch tables, two generations: a batch's host->device table copies
@@ -172,9 +175,11 @@ struct mim_ctx {
     Arena arena;
     std::vector<SetRec> sets;
     // batch workspace
-    DevBuf probs, works, parts, good_q, good_t, pts, n_good, results, masks, knn_idx, knn_dist, inl_tab, inl_out, knn_ctr;
+    DevBuf probs, works, parts, good_q, good_t, pts, n_good, results, masks, knn_idx, knn_dist, inl_tab, inl_out, knn_ctr, ham_works;
     RansacWs rws;
     std::vector<ProbDev> h_probs;
+    int n_ham_works = 0;  // Hamming work items of the current batch (its binary problems)
+    int n_cu = 0;         // compute units of the device (first batch)
     int n_works = 0;  // distance segments of the current batch (works, then the per-block segment starts)
     std::vector<long long> h_good_off;
     PinnedStage stage;
@@ -303,7 +308,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -422,6 +427,55 @@ mim_status mim_set_create(mim_ctx* c, const float* desc, const float* kp, int32_
     return set_create_locked(c, desc, kp, n, dim, on_device, set_id);
 }
 
+// A binary set: rows copied into the library's own storage (never borrowed), zero-padded to 16, 32 or
+// 64 bytes, with zero rows up to the next multiple of kHamTileRows (the Hamming kernel stages whole
+// tiles).  No prep job: the kernel reads the padded rows as they are.
+static mim_status set_create_bin_locked(mim_ctx* c, const uint8_t* desc, int64_t step, const float* kp, int32_t n,
+                                        int32_t width, int32_t on_device, int32_t* set_id) {
+    if (!set_id || n < 0 || (n > 0 && (!desc || !kp))) return fail(c, MIM_EINVAL, "set_create_bin: bad arguments");
+    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "set_create_bin: width must be 1..64 bytes (got %d)", width);
+    if (step < width)
+        return fail(c, MIM_EINVAL, "set_create_bin: step %lld < width %d", (long long)step, width);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int pad = width <= 16 ? 16 : width <= 32 ? 32 : 64;
+    const size_t rows = (size_t)std::max((n + kHamTileRows - 1) / kHamTileRows, 1) * kHamTileRows;
+    SetRec r{};
+    r.mark = c->arena.pos();
+    r.bin_pad = pad;
+    r.bin_width = width;
+    r.d.n = n;
+    r.d.n_tiles = (n + 63) / 64;
+    void *dd = nullptr, *dk = nullptr;
+    auto undo = [&](mim_status st) {
+        c->arena.seek(r.mark);
+        return st;
+    };
+    if (c->arena.alloc(rows * pad, &dd) != hipSuccess || c->arena.alloc((size_t)std::max(n, 1) * sizeof(float2), &dk) != hipSuccess)
+        return undo(fail(c, MIM_ENOMEM, "set_create_bin: device allocation of %zu bytes failed", rows * pad));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipError_t e = hipMemsetAsync(dd, 0, rows * pad, c->stream);
+    if (e == hipSuccess && n > 0)
+        e = hipMemcpy2DAsync(dd, (size_t)pad, desc, (size_t)step, (size_t)width, (size_t)n, kind, c->stream);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dk, kp, (size_t)n * sizeof(float2), kind, c->stream);
+    if (e == hipSuccess && !on_device) e = hipStreamSynchronize(c->stream);  // host buffers may go away
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        return undo(fail(c, MIM_EDEVICE, "set_create_bin: copy failed: %s", hipGetErrorString(e)));
+    }
+    r.d.frag = (const int8_t*)dd;
+    r.d.kp = (const float2*)dk;
+    *set_id = (int32_t)c->sets.size();
+    c->sets.push_back(r);
+    return MIM_OK;
+}
+
+mim_status mim_set_create_bin(mim_ctx* c, const uint8_t* desc, int64_t step, const float* kp, int32_t n, int32_t width,
+                              int32_t on_device, int32_t* set_id) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return set_create_bin_locked(c, desc, step, kp, n, width, on_device, set_id);
+}
+
 static void sets_truncate_locked(mim_ctx* c, int n_keep);
 
 mim_status mim_sets_create(mim_ctx* c, int32_t count, const float* const* desc, const float* const* kp,
@@ -519,6 +573,8 @@ mim_status mim_set_rows(mim_ctx* c, int32_t set_id, int32_t cap, float* desc, fl
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_id < 0 || set_id >= (int)c->sets.size())
         return fail(c, MIM_EINVAL, "set_rows: set %d not registered (%d sets)", set_id, (int)c->sets.size());
+    if (c->sets[set_id].bin_pad)
+        return fail(c, MIM_EINVAL, "set_rows: set %d holds binary descriptors, not float rows", set_id);
     HIPCHK(c, hipSetDevice(c->device));
     const SetDev& d = c->sets[set_id].d;
     *n_rows = d.n;
@@ -544,9 +600,14 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         hipDeviceProp_t prop;
         HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
         c->knn_grid = std::max(1, prop.multiProcessorCount * std::max(1, knn_blocks_per_cu()));
+        c->n_cu = std::max(1, prop.multiProcessorCount);
     }
     c->h_probs.assign(n, ProbDev{});
     long long part = 0, good = 0, it = 0, units = 0;
+    // binary problems (both sets binary, one width) are known here, on the host: they stay out of the
+    // i8 schedule below and get the Hamming work list after it
+    std::vector<char> bin(n, 0);
+    long long ham_qb = 0;  // their query blocks
     for (int i = 0; i < n; ++i) {
         const int qs = problems[i].query_set, ts = problems[i].train_set;
         if (qs < 0 || qs >= (int)c->sets.size() || ts < 0 || ts >= (int)c->sets.size())
@@ -554,6 +615,18 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         if (c->sets[ts].d.n >= (1 << 18))  // BFMatcher::knnMatchImpl: train rows < 1 << 18 (IMGIDX_SHIFT)
             return fail(c, MIM_EINVAL, "problem %d: train set of %d rows exceeds OpenCV's 2^18 limit", i,
                         c->sets[ts].d.n);
+        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
+        if ((Q.bin_pad != 0) != (T.bin_pad != 0))
+            return fail(c, MIM_EINVAL, "problem %d: set %d holds %s descriptors and set %d %s ones", i, qs,
+                        Q.bin_pad ? "binary" : "float", ts, T.bin_pad ? "binary" : "float");
+        if (Q.bin_width != T.bin_width)
+            return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
+                        T.bin_width);
+        if (Q.bin_pad) {
+            bin[i] = 1;
+            ham_qb += (Q.d.n + kHamBlockQ - 1) / kHamBlockQ;
+            continue;
+        }
         units += (long long)((c->sets[qs].d.n + kKnnBlockQ - 1) / kKnnBlockQ) * c->sets[ts].d.n_tiles;
     }
     // Balanced distance schedule.  The (problem, query block, train tile) units are cut into equal
@@ -578,7 +651,7 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     // MIM_KNN_DYN=0 / 1 forces either.
     long long n_sweeps = 0;
     for (int i = 0; i < n; ++i)
-        n_sweeps += (c->sets[problems[i].query_set].d.n + kKnnBlockQ - 1) / kKnnBlockQ;
+        if (!bin[i]) n_sweeps += (c->sets[problems[i].query_set].d.n + kKnnBlockQ - 1) / kKnnBlockQ;
     const char* dyn_env = getenv("MIM_KNN_DYN");
     const bool dyn = dyn_env ? atoi(dyn_env) != 0 : n_sweeps >= c->knn_grid;
     const long long G = c->knn_grid;
@@ -603,6 +676,23 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         ProbDev& P = c->h_probs[i];
         P.q = c->sets[problems[i].query_set].d;
         P.t = c->sets[problems[i].train_set].d;
+        if (bin[i]) {
+            // Train rows are cut into splits only while the query blocks alone would leave CUs idle (one
+            // 64 x 70,000 problem must not run on one block): about four work items per CU over the
+            // batch's binary problems, a split no shorter than four tiles.
+            const int hq = (P.q.n + kHamBlockQ - 1) / kHamBlockQ;
+            const int tiles = (P.t.n + kHamTileRows - 1) / kHamTileRows;
+            const long long want = (4LL * c->n_cu + ham_qb - 1) / std::max<long long>(ham_qb, 1);
+            P.nsplit = (int)std::max<long long>(1, std::min<long long>(want, tiles / 4));
+            P.q_pad = std::max(hq, 1) * kHamBlockQ;
+            P.part_off = part;
+            part += (long long)P.nsplit * P.q_pad;
+            P.good_off = good;
+            good += (std::max(P.q.n, 1) + 31) & ~31;
+            P.it_off = it;
+            it += std::max(max_iters, 1);
+            continue;
+        }
         const int qb = (P.q.n + kKnnBlockQ - 1) / kKnnBlockQ, nt = P.t.n_tiles;
         const int nseg = (sub_target >= 0 && nt > sub) ? (int)((nt + sub - 1) / sub) : 1;
         const int lseg = nseg > 1 ? (nt + nseg - 1) / nseg : nt;
@@ -660,11 +750,15 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         int tail_from = n, ksplit = 1;
         if (tail_env && atoi(tail_env) != 0 && n_sweeps > G && rem > 0) {
             long long ts = 0;
-            while (tail_from > 0 && ts < rem) ts += c->h_probs[--tail_from].q_pad / kKnnBlockQ;
+            while (tail_from > 0 && ts < rem) {
+                --tail_from;
+                if (!bin[tail_from]) ts += c->h_probs[tail_from].q_pad / kKnnBlockQ;
+            }
             ksplit = (int)std::max<long long>(2, std::min<long long>(8, (G + ts / 2) / ts));
         }
         long long total = 0, total_t = 0;
         for (int i = 0; i < n; ++i) {
+            if (bin[i]) continue;
             ProbDev& P = c->h_probs[i];
             const int qb = P.q_pad / kKnnBlockQ;
             P.nsplit = 1;
@@ -674,6 +768,7 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         }
         std::vector<KnnWork> tail;
         for (int i = tail_from; i < n; ++i) {  // pieces in (problem, tile range, query block) order
+            if (bin[i]) continue;
             ProbDev& P = c->h_probs[i];
             const int qb = P.q_pad / kKnnBlockQ, nt = P.t.n_tiles, k = std::min(ksplit, std::max(nt, 1));
             P.nsplit = k;
@@ -722,6 +817,24 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     HIPCHK(c, c->probs.ensure(sizeof(ProbDev) * std::max(n, 1)));
     HIPCHK(c, c->works.ensure(sizeof(KnnWork) * std::max<size_t>(works.size(), 1) + sizeof(int) * seg.size()));
     HIPCHK(c, c->parts.ensure(sizeof(Top2) * std::max<long long>(part, 1)));
+    // Hamming work list of the binary problems: (problem, query block, train row range of one split)
+    std::vector<HamWork> ham;
+    for (int i = 0; i < n; ++i) {
+        if (!bin[i]) continue;
+        const ProbDev& P = c->h_probs[i];
+        const int hq = (P.q.n + kHamBlockQ - 1) / kHamBlockQ;
+        const int tiles = (P.t.n + kHamTileRows - 1) / kHamTileRows;
+        const int wdw = c->sets[problems[i].query_set].bin_pad / 4;
+        for (int sp = 0; sp < P.nsplit; ++sp) {
+            const int r0 = (int)((long long)sp * tiles / P.nsplit) * kHamTileRows;
+            const int r1 = std::min(P.t.n, (int)((long long)(sp + 1) * tiles / P.nsplit) * kHamTileRows);
+            for (int b = 0; b < hq; ++b)
+                ham.push_back(HamWork{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
+                                      c->parts.as<Top2>() + P.part_off + (long long)sp * P.q_pad, P.q.n,
+                                      b * kHamBlockQ, r0, std::max(r0, r1), wdw, 0});
+        }
+    }
+    if (!ham.empty()) HIPCHK(c, c->ham_works.ensure(sizeof(HamWork) * ham.size()));
     HIPCHK(c, c->good_q.ensure(sizeof(int32_t) * good));
     HIPCHK(c, c->good_t.ensure(sizeof(int32_t) * good));
     HIPCHK(c, c->pts.ensure(sizeof(float4) * good));
@@ -729,13 +842,19 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     HIPCHK(c, c->masks.ensure(good));
     // the device tables are rewritten in stream order (after the previous batch's kernels)
     const size_t pb = sizeof(ProbDev) * n, wb = sizeof(KnnWork) * works.size(), sb = sizeof(int) * seg.size();
+    const size_t hb = sizeof(HamWork) * ham.size();
     char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + wb + sb, &st));
+    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb, &st));
     memcpy(st, c->h_probs.data(), pb);
     memcpy(st + pb, works.data(), wb);
     memcpy(st + pb + wb, seg.data(), sb);
     HIPCHK(c, hipMemcpyAsync(c->probs.p, st, pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->works.p, st + pb, wb + sb, hipMemcpyHostToDevice, c->stream));
+    if (hb) {
+        memcpy(st + pb + wb + sb, ham.data(), hb);
+        HIPCHK(c, hipMemcpyAsync(c->ham_works.p, st + pb + wb + sb, hb, hipMemcpyHostToDevice, c->stream));
+    }
+    c->n_ham_works = (int)ham.size();
     HIPCHK(c, c->stage.release_after(c->stream));
     c->h_good_off.resize(n);
     for (int i = 0; i < n; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
@@ -787,6 +906,7 @@ static void knn_launch(mim_ctx* c) {
     const KnnWork* w = c->works.as<KnnWork>();
     launch_knn(c->probs.as<ProbDev>(), w, c->n_works, reinterpret_cast<const int*>(w + c->n_works), c->n_knn_blocks,
                c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, c->cur);
+    launch_knn_hamming(c->ham_works.as<HamWork>(), c->n_ham_works, c->cur);
 }
 
 // distance + ratio kernels of the batch's problems
@@ -839,6 +959,51 @@ mim_status mim_knn2_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, i
     c->last_gen = -1;
     c->last_fh = false;
     return MIM_OK;
+}
+
+mim_status mim_knn2_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
+                            int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
+        return fail(c, MIM_EINVAL, "knn2_hamming: bad arguments");
+    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "knn2_hamming: width must be 1..64 bytes (got %d)", width);
+    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    // private sets appended after the user's sets, removed afterwards (as mim_knn2_l2)
+    const size_t base = c->sets.size();
+    const Arena::Mark mark = c->arena.pos();
+    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
+    // float sets still waiting for their prep get a flags block from the arena at build_tables, after
+    // the private sets' storage: then that storage stays until the next clear, as mim_knn2_l2's does
+    const bool reclaim = c->pend.empty();
+    auto run = [&]() -> mim_status {
+        int32_t sq, st;
+        mim_status s = set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, &sq);
+        if (s != MIM_OK) return s;
+        s = set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, &st);
+        if (s != MIM_OK) return s;
+        mim_problem pr{sq, st};
+        s = build_tables(c, &pr, 1, 1);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * 2 * nq));
+        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * 2 * nq));
+        s = knn_ratio_locked(c, 1, 0.9f, true);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return MIM_OK;
+    };
+    const mim_status s = run();
+    ev_collect(c);
+    // the private sets own their storage and nothing was registered after them: both go
+    c->sets.resize(base);
+    if (reclaim) c->arena.seek(mark);
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    return s;
 }
 
 mim_status mim_ratio_filter(mim_ctx* c, const int32_t* idx, const float* dist, int32_t nq, float ratio,

@@ -1,0 +1,129 @@
+// hamming.hip — brute-force 2-NN over binary descriptors (BFMatcher(NORM_HAMMING).knnMatch, k = 2).
+//
+// Rows are CV_8U descriptors (ORB, BRIEF, BRISK, FREAK, AKAZE, LATCH) zero-padded to 16, 32 or 64 bytes
+// (DESIGN.md "Binary descriptors").  The distance is popcount(q ^ t) summed over the row's dwords, an
+// integer <= 512, so everything is exact.  Output: the same Top2 partials [split][q_pad] that
+// ratio_compact_kernel / knn_emit_kernel (knn.hip) merge; key = (float)distance, sentinels
+// FLT_MAX / INT_MAX.  gfx950, wave64.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <climits>
+
+#include "mim_internal.h"
+
+namespace mim {
+
+namespace {
+
+constexpr int kHamThreads = 256;                  // 4 waves
+constexpr int kHamWaves = kHamThreads / kWave;
+constexpr int kHamQPT = kHamBlockQ / kWave;       // query rows held by one lane
+constexpr uint32_t kHamNone = 0xFFFFFFFFu;        // packed-key sentinel: no row
+static_assert(kHamQPT * kWave == kHamBlockQ, "a block's queries are whole waves of lanes");
+static_assert(kHamTileRows * 64 >= kHamWaves * kHamBlockQ * 8, "the merge scratch reuses the tile's LDS");
+
+// popcount(x) + acc as the one instruction it is (left to the compiler, the sums are reassociated into
+// popcounts plus separate three-operand adds: 23 instead of 20 VALU instructions per pair at 32 bytes)
+__device__ __forceinline__ uint32_t popc_add(uint32_t x, uint32_t acc) {
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+    return r;
+}
+
+// One work item for rows of W dwords.  Every wave holds the same kHamBlockQ queries (lane l: rows
+// q0 + l + 64 j, j < kHamQPT, in VGPRs) and takes every kHamWaves-th train row of the staged tile, read
+// from LDS at a wave-uniform address (a broadcast: no bank conflicts), so one ds_read_b128 feeds
+// 4 dwords x kHamQPT queries of xor + popcount.  Top-2 per query as packed keys d << 18 | row
+// (d <= 512, row < 2^18): min/max keep the two smallest keys, and key order is (distance, row) order,
+// which is BFMatcher's tie rule (an equal distance never displaces an earlier row).
+template <int W>
+__device__ __forceinline__ void ham_work(const HamWork& w, uint32_t* lds) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t q[kHamQPT][W];
+#pragma unroll
+    for (int j = 0; j < kHamQPT; ++j) {
+        const int qi = w.q0 + j * kWave + lane;
+        const bool ok = qi < w.nq;
+#pragma unroll
+        for (int k = 0; k < W; k += 4) {
+            const uint4 v = ok ? *reinterpret_cast<const uint4*>(w.q + (size_t)qi * W + k) : make_uint4(0, 0, 0, 0);
+            q[j][k] = v.x; q[j][k + 1] = v.y; q[j][k + 2] = v.z; q[j][k + 3] = v.w;
+        }
+    }
+    uint32_t k1[kHamQPT], k2[kHamQPT];
+#pragma unroll
+    for (int j = 0; j < kHamQPT; ++j) k1[j] = k2[j] = kHamNone;
+
+    // train rows [r0, r1): r0 is a multiple of kHamTileRows, and the set's storage is zero rows up to
+    // the next multiple past its last row, so a whole tile is always readable
+    for (int r = w.r0; r < w.r1; r += kHamTileRows) {
+        __syncthreads();
+        const uint4* src = reinterpret_cast<const uint4*>(w.t + (size_t)r * W);
+        for (int e = tid; e < kHamTileRows * W / 4; e += kHamThreads) reinterpret_cast<uint4*>(lds)[e] = src[e];
+        __syncthreads();
+        const int rows = min(kHamTileRows, w.r1 - r);
+        for (int rr = wave; rr < rows; rr += kHamWaves) {
+            uint32_t t[W];
+#pragma unroll
+            for (int k = 0; k < W; k += 4) {
+                const uint4 v = *reinterpret_cast<const uint4*>(lds + rr * W + k);
+                t[k] = v.x; t[k + 1] = v.y; t[k + 2] = v.z; t[k + 3] = v.w;
+            }
+            const uint32_t row = (uint32_t)(r + rr);
+#pragma unroll
+            for (int j = 0; j < kHamQPT; ++j) {
+                uint32_t d = __popc(q[j][0] ^ t[0]);
+#pragma unroll
+                for (int k = 1; k < W; ++k) d = popc_add(q[j][k] ^ t[k], d);
+                const uint32_t key = (d << 18) | row;
+                k2[j] = min(k2[j], max(k1[j], key));
+                k1[j] = min(k1[j], key);
+            }
+        }
+    }
+
+    // merge the waves' lists: slot s = 64 j + lane is query q0 + s
+    __syncthreads();
+    uint2* mg = reinterpret_cast<uint2*>(lds);  // [wave][slot]
+#pragma unroll
+    for (int j = 0; j < kHamQPT; ++j) mg[wave * kHamBlockQ + j * kWave + lane] = make_uint2(k1[j], k2[j]);
+    __syncthreads();
+    for (int s = tid; s < kHamBlockQ; s += kHamThreads) {
+        uint32_t a1 = kHamNone, a2 = kHamNone;
+#pragma unroll
+        for (int v = 0; v < kHamWaves; ++v) {
+            const uint2 m = mg[v * kHamBlockQ + s];
+            a2 = min(a2, max(a1, m.x));
+            a1 = min(a1, m.x);
+            a2 = min(a2, max(a1, m.y));
+            a1 = min(a1, m.y);
+        }
+        const int qi = w.q0 + s;
+        if (qi < w.nq) {
+            Top2 o;
+            o.k1 = a1 == kHamNone ? FLT_MAX : (float)(a1 >> 18);
+            o.i1 = a1 == kHamNone ? INT_MAX : (int)(a1 & 0x3FFFFu);
+            o.k2 = a2 == kHamNone ? FLT_MAX : (float)(a2 >> 18);
+            o.i2 = a2 == kHamNone ? INT_MAX : (int)(a2 & 0x3FFFFu);
+            w.out[qi] = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kHamThreads) void knn2_hamming_kernel(const HamWork* __restrict__ works) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kHamTileRows * 16];
+    const HamWork w = works[blockIdx.x];
+    if (w.wdw == 4) ham_work<4>(w, lds);  // block-uniform
+    else if (w.wdw == 8) ham_work<8>(w, lds);
+    else ham_work<16>(w, lds);
+}
+
+}  // namespace
+
+void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st) {
+    if (n_works > 0) knn2_hamming_kernel<<<n_works, kHamThreads, 0, st>>>(works);
+}
+
+}  // namespace mim

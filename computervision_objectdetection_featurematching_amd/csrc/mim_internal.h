@@ -78,6 +78,26 @@ struct KnnWork {
     int split;
 };
 
+// Binary descriptor sets (hamming.hip, DESIGN.md "Binary descriptors").  Such a set's SetDev has
+// frag = its rows zero-padded to 16, 32 or 64 bytes (zero rows up to the next multiple of kHamTileRows
+// past the last row), kp and n; norm, f32 and flags are null.  The padded width is host knowledge
+// (api.cpp SetRec), carried to the device in each work item.
+constexpr int kHamBlockQ = 256;    // queries per Hamming work item
+constexpr int kHamTileRows = 128;  // train rows per LDS stage
+
+// Work item of the Hamming kernel: kHamBlockQ queries from q0 x train rows [r0, r1) of one problem,
+// written to one train split.  r0 is a multiple of kHamTileRows.
+struct HamWork {
+    const uint32_t* q;   // padded query rows of the problem
+    const uint32_t* t;   // padded train rows
+    Top2* out;           // the split's partials: parts + part_off + split * q_pad
+    int nq;
+    int q0;
+    int r0, r1;
+    int wdw;             // dwords per padded row: 4, 8 or 16
+    int pad_;
+};
+
 // RANSAC state per problem (RANSACPointSetRegistrator::run locals, ptsetreg.cpp).
 struct RansacState {
     long long stream_pos;  // RNG draws consumed so far (all calls see RNG((uint64)-1))

@@ -128,6 +128,55 @@ class Matcher:
         self._n_sets = sid.value + 1
         return sid.value
 
+    def add_binary_set(self, desc_u8, kp) -> int:
+        """Register a set of binary descriptors (mim_set_create_bin): CV_8U rows of 1..64 bytes (ORB 32,
+        BRIEF 16/32/64, AKAZE 61, BRISK/FREAK 64) matched with NORM_HAMMING, and their (n, 2) keypoints.
+
+        numpy arrays (uint8 (n, width), any row stride; float32 keypoints), or torch device tensors (uint8
+        (n, width) with unit column stride, contiguous float32 (n, 2)).  The rows are copied, never
+        borrowed: device tensors may be released once the matcher's stream has passed the copy."""
+        on_dev = int(hasattr(desc_u8, "is_cuda") and desc_u8.is_cuda)
+        if not on_dev:
+            desc = np.asarray(desc_u8)
+            if desc.dtype != np.uint8 or desc.ndim != 2:
+                raise ValueError(f"add_binary_set: descriptors must be a uint8 (n, width) array, got {desc.dtype} "
+                                 f"{desc.shape}")
+            if desc.shape[0] <= 1 or desc.strides[1] != 1 or desc.strides[0] < desc.shape[1]:
+                desc = np.ascontiguousarray(desc)  # anything but rows of unit-stride bytes a fixed step apart
+            kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 2)
+            step = int(desc.strides[0])
+        else:
+            import torch
+            desc = desc_u8
+            if not (hasattr(kp, "is_cuda") and kp.is_cuda):
+                raise ValueError("add_binary_set: keypoints must be on the device when the descriptors are")
+            if desc.dtype != torch.uint8 or desc.dim() != 2 or (desc.shape[0] > 1 and desc.stride(1) != 1):
+                raise ValueError(f"add_binary_set: descriptors must be a uint8 (n, width) tensor with unit column "
+                                 f"stride, got {desc.dtype} {tuple(desc.shape)}")
+            if kp.dtype != torch.float32 or not kp.is_contiguous() or kp.dim() != 2 or kp.shape[1] != 2:
+                raise ValueError(f"add_binary_set: keypoints must be a contiguous float32 (n, 2) tensor, got "
+                                 f"{kp.dtype} {tuple(kp.shape)}")
+            for name, t in (("descriptors", desc), ("keypoints", kp)):
+                if t.device.index != self.device:
+                    raise ValueError(f"add_binary_set: {name} on {t.device}, matcher on cuda:{self.device}")
+            step = int(desc.stride(0)) if desc.shape[0] > 1 else int(desc.shape[1])
+            mine = torch.cuda.ExternalStream(self.stream_handle(), device=desc.device)
+            cur = torch.cuda.current_stream(desc.device)
+            if cur.cuda_stream != mine.cuda_stream:
+                mine.wait_stream(cur)
+        if int(kp.shape[0]) != int(desc.shape[0]):
+            raise ValueError("add_binary_set: descriptor and keypoint row counts differ")
+        sid = C.c_int32()
+        self._check(self.L.mim_set_create_bin(self._ctx, C.c_void_p(_lib.ptr(desc)), step, C.c_void_p(_lib.ptr(kp)),
+                                              int(desc.shape[0]), int(desc.shape[1]), on_dev, C.byref(sid)))
+        if on_dev:
+            # copied on the matcher's stream: kept until that stream has passed the copy
+            ev = torch.cuda.Event()
+            ev.record(mine)
+            self._retired.append((ev, [desc, kp]))
+        self._n_sets = sid.value + 1
+        return sid.value
+
     def add_sets(self, pairs) -> list[int]:
         """Register several sets in one library call (mim_sets_create), as add_set in order: every pair
         (desc, kp) numpy (host) or every pair torch (device), the same rules per pair; all or nothing."""
@@ -222,6 +271,31 @@ class Matcher:
         if k != 2:
             raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
         idx, dist = self.knn_match_arrays(query, train)
+        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
+                for i in range(idx.shape[0])]
+
+    def knn_match_hamming_arrays(self, query, train):
+        """BFMatcher(NORM_HAMMING).knnMatch(query, train, k=2) on uint8 rows of one width (1..64 bytes),
+        as arrays: idx (nq, 2) int32 (-1 absent), dist (nq, 2) float32 (the integer distances)."""
+        q, t = np.asarray(query), np.asarray(train)
+        if q.dtype != np.uint8 or t.dtype != np.uint8 or q.ndim != 2 or t.ndim != 2:
+            raise ValueError("knn_match_hamming: uint8 (n, width) arrays are required")
+        if q.shape[1] != t.shape[1]:
+            raise ValueError(f"knn_match_hamming: query rows of {q.shape[1]} bytes, train rows of {t.shape[1]}")
+        q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
+        nq = q.shape[0]
+        idx = np.full((max(nq, 1), 2), -1, np.int32)
+        dist = np.zeros((max(nq, 1), 2), np.float32)
+        self._check(self.L.mim_knn2_hamming(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                            t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
+                                            C.c_void_p(dist.ctypes.data)))
+        return idx[:nq], dist[:nq]
+
+    def knn_match_hamming(self, query, train, k: int = 2):
+        """BFMatcher(NORM_HAMMING).knnMatch(query, train, matches, k=2) -> list of lists of DMatch."""
+        if k != 2:
+            raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
+        idx, dist = self.knn_match_hamming_arrays(query, train)
         return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
                 for i in range(idx.shape[0])]
 

@@ -184,3 +184,55 @@ CONFIGS = {
     "c4": dict(n_models=1, n_scenes=256, nq=10000, nt=10000, n_plant=2000, max_iters=50000, sharded=True),
     "c5": dict(n_models=1, n_scenes=1, nq=50000, nt=50000, n_plant=0, max_iters=0, knn_only=True),
 }
+
+
+# ---- binary descriptors (ORB, BRIEF, BRISK, FREAK, AKAZE: CV_8U rows matched with NORM_HAMMING) ----
+def orb_like(rng: np.random.Generator, n: int, width: int = 32) -> np.ndarray:
+    """n rows of `width` uniform random bytes: two such rows of 32 bytes differ in 128 +- 8 bits."""
+    return rng.integers(0, 256, size=(n, width), dtype=np.uint8)
+
+
+def flip_bits(rng: np.random.Generator, rows: np.ndarray, max_flips: int) -> np.ndarray:
+    """A copy of the uint8 rows with 0..max_flips distinct bits of each row flipped."""
+    out = rows.copy()
+    nbits = out.shape[1] * 8
+    k = rng.integers(0, max_flips + 1, size=out.shape[0])
+    for i in range(out.shape[0]):
+        bits = rng.choice(nbits, size=k[i], replace=False)
+        np.bitwise_xor.at(out[i], bits >> 3, (1 << (bits & 7)).astype(np.uint8))
+    return out
+
+
+def make_binary_dataset(n_models: int, n_scenes: int, nq: int, nt: int, n_plant: int, inlier_frac: float = 0.5,
+                        width: int = 32, max_flips: int = 20, seed: int = SEED_BASE) -> Dataset:
+    """make_dataset with binary descriptors: every scene holds, for every model, the model's first
+    ``n_plant`` rows with at most ``max_flips`` bits flipped (~20 of 256: far inside the ~100 bits of the
+    nearest random row, so they pass the 0.9 ratio) at random positions, the rest uniform random rows
+    (which fail it).  Keypoints and the planted geometry as make_dataset."""
+    if n_models * n_plant > nt or n_plant > nq:
+        raise ValueError("planted rows do not fit")
+    mrng = np.random.default_rng(seed)
+    model_desc, model_kp = [], []
+    for _ in range(n_models):
+        model_desc.append(orb_like(mrng, nq, width))
+        model_kp.append(np.c_[mrng.uniform(0, IMG_W, nq), mrng.uniform(0, IMG_H, nq)].astype(np.float32))
+    n_inl = int(round(inlier_frac * n_plant))
+    scene_desc, scene_kp = [], []
+    H_true = np.zeros((n_models, n_scenes, 3, 3))
+    plant_pos = np.zeros((n_models, n_scenes, n_plant), dtype=np.int64)
+    for s in range(n_scenes):
+        srng = np.random.default_rng(seed + 1 + s)
+        d = orb_like(srng, nt, width)
+        kp = np.c_[srng.uniform(0, IMG_W, nt), srng.uniform(0, IMG_H, nt)].astype(np.float32)
+        pos = srng.permutation(nt)[: n_models * n_plant].reshape(n_models, n_plant)
+        for m in range(n_models):
+            d[pos[m]] = flip_bits(srng, model_desc[m][:n_plant], max_flips)
+            H = random_homography(srng)
+            H_true[m, s] = H
+            inl = srng.choice(n_plant, size=n_inl, replace=False)
+            proj = apply_h(H, model_kp[m][inl])
+            kp[pos[m][inl]] = proj + srng.uniform(-0.5, 0.5, size=proj.shape).astype(np.float32)
+            plant_pos[m, s] = pos[m]
+        scene_desc.append(d)
+        scene_kp.append(kp)
+    return Dataset(model_desc, model_kp, scene_desc, scene_kp, H_true, plant_pos, n_plant, n_inl)

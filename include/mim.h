@@ -13,10 +13,12 @@
  *   - Host buffers are owned by the caller.  Device buffers inside a ctx are owned by the ctx.
  *   - One ctx = one GPU + one HIP stream; calls on one ctx are serialised by an internal mutex.
  *   - `_dev`/batch calls are asynchronous on the ctx stream; mim_synchronize() waits.
- *   - Descriptors must be CV_32F rows of dim 128 (SIFT).  Integer-valued rows in [0,255] (what
- *     OpenCV SIFT emits) take the exact-integer i8-MFMA path (v_mfma_i32_32x32x32_i8); any other
- *     rows take the fp32 path in OpenCV's SSE summation order.  Either way indices and distances
- *     are bit-identical to the CPU restatement in oracle/.
+ *   - Descriptors are CV_32F rows of dim 128 (SIFT, matched with NORM_L2) or CV_8U rows of 1..64
+ *     bytes (ORB, BRIEF, BRISK, FREAK, AKAZE, LATCH, matched with NORM_HAMMING: mim_set_create_bin,
+ *     mim_knn2_hamming).  Float rows: integer-valued rows in [0,255] (what OpenCV SIFT emits) take
+ *     the exact-integer i8-MFMA path (v_mfma_i32_32x32x32_i8); any other rows take the fp32 path in
+ *     OpenCV's SSE summation order.  Binary rows: xor + popcount, integer throughout.  Every way
+ *     indices and distances are bit-identical to the CPU restatement (oracle/, tests/hamming_ref.py).
  */
 #ifndef MIM_H
 #define MIM_H
@@ -116,6 +118,18 @@ mim_status mim_set_create(struct mim_ctx* ctx, const float* desc, const float* k
  * scene sets (processAllModelsImages' views, a batch of scenes) without a call per set. */
 mim_status mim_sets_create(struct mim_ctx* ctx, int32_t count, const float* const* desc, const float* const* kp_xy,
                            const int32_t* rows, int32_t dim, int32_t on_device, int32_t* first_id);
+/* A set of n binary descriptors: rows of `width` bytes (1 <= width <= 64: BRIEF 16/32/64, ORB 32,
+ * AKAZE 61, BRISK/FREAK 64), row stride `step` bytes >= width, with their n x 2 float keypoints.
+ * The CV_8U rows that BFMatcher(NORM_HAMMING) matches.  Ids come from the same sequence as float sets',
+ * and mim_sets_clear / _truncate / _info treat the set as any other.  A binary set never borrows: rows
+ * (zero-padded to 16, 32 or 64 bytes) and keypoints are copied on the ctx stream into the library's
+ * storage.  on_device == 0: host pointers, copied before the call returns; on_device != 0: device
+ * pointers whose producer must be ordered before the ctx stream (they may be released once the ctx
+ * stream has passed the copies).  A problem's two sets must both be binary, of one width (else
+ * MIM_EINVAL at mim_batch_run / mim_knn2_sets_dev); a batch may mix such problems with float ones.
+ * MIM_EINVAL for width outside 1..64 or step < width. */
+mim_status mim_set_create_bin(struct mim_ctx* ctx, const uint8_t* desc, int64_t step, const float* kp_xy,
+                              int32_t n, int32_t width, int32_t on_device, int32_t* set_id);
 mim_status mim_sets_clear(struct mim_ctx* ctx);
 /* Drops the sets registered after the first n_keep (ids >= n_keep) and reuses their device storage;
  * the first n_keep keep their ids and layout.  The same rules as mim_sets_clear for work already
@@ -131,7 +145,7 @@ mim_status mim_sets_info(struct mim_ctx* ctx, int32_t* n_sets, int64_t* generati
 /* Debug/test copy-out of set `set_id`: its n float32 descriptor rows (n x 128, row-major) and keypoint
  * positions (n x 2) as the kernels read them, e.g. the device-registered scene scales of
  * mim_sift_scales_sets.  Writes min(n, cap) rows (either output may be NULL); *n_rows = n.  Waits for
- * the ctx stream. */
+ * the ctx stream.  MIM_EINVAL for a binary set (mim_set_create_bin): it has no float rows. */
 mim_status mim_set_rows(struct mim_ctx* ctx, int32_t set_id, int32_t cap, float* desc, float* kp_xy, int32_t* n_rows);
 
 /* ---- primitive ops, host buffers, synchronous ------------------------------------------------
@@ -142,7 +156,12 @@ mim_status mim_set_rows(struct mim_ctx* ctx, int32_t set_id, int32_t cap, float*
  * idx[2i+k] = trainIdx of the k-th match of query i (-1 if absent), dist[2i+k] = DMatch::distance. */
 mim_status mim_knn2_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const float* t, int32_t nt,
                        int32_t dim, int32_t* idx, float* dist);
-/* ≙ the ratio-test loop                                        TestsDetector.cpp:66-72
+/* ≙ BFMatcher(NORM_HAMMING).knnMatch(q, t, matches, 2) on CV_8U rows of `width` bytes (1..64, dense).
+ * Distances are the integer popcount of the XOR as float; equal distances keep the lower train index
+ * (first and second place); outputs as mim_knn2_l2. */
+mim_status mim_knn2_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
+                            int32_t width, int32_t* idx, float* dist);
+/* ≙ the ratio-test loop                                     TestsDetector.cpp:66-72
  * Writes queryIdx/trainIdx of survivors in ascending query order; *n_good = goodMatches.size(). */
 mim_status mim_ratio_filter(struct mim_ctx* ctx, const int32_t* idx, const float* dist, int32_t nq,
                             float ratio, int32_t* q_out, int32_t* t_out, int32_t* n_good);

@@ -28,11 +28,16 @@
 
 namespace mim {
 
-// One view of an ObjectModel: n keypoints (KeyPoint::pt) + n x 128 CV_32F descriptors.
+// One view of an ObjectModel: n keypoints (KeyPoint::pt) + their descriptors, either n x 128 CV_32F
+// (SIFT, `descriptors`) or n CV_8U rows of bin_width bytes (ORB, BRIEF, BRISK, FREAK, AKAZE:
+// `bin_descriptors`, matched with NORM_HAMMING) — one of the two, never both.
 struct View {
     std::vector<Point2f> keypoints;
-    std::vector<float> descriptors;  // row-major n x 128
+    std::vector<float> descriptors;        // row-major n x 128
+    std::vector<uint8_t> bin_descriptors;  // row-major n x bin_width, dense
+    int bin_width = 0;                     // bytes per binary row (1..64); 0: a float view
     int size() const { return (int)keypoints.size(); }
+    bool binary() const { return bin_width != 0; }
 };
 
 // An object's identity for the Detector's registered-views cache: every constructed, copied, moved or
@@ -86,8 +91,8 @@ class Detector {
 
     // The model views registered by the last detect_* call are reused while the next call passes the
     // same ModelViews objects (identity, not address: see ObjectIdentity) whose every view has the same
-    // descriptor and keypoint storage (pointers and sizes) and the same sampled rows (first, middle and
-    // last descriptor row and keypoint), and nobody else has dropped sets of this ctx (mim_sets_info's
+    // descriptor (float or binary) and keypoint storage (pointers and sizes) and the same sampled rows
+    // (first, middle and last descriptor row and keypoint), and nobody else has dropped sets of this ctx (mim_sets_info's
     // generation).  A caller that rewrites view contents in place calls this first, so the next call
     // registers them anew: the sampled rows catch most rewrites, not all.
     void invalidate_models() { reg_n_ = -1; }
@@ -100,10 +105,15 @@ class Detector {
         out_pts.insert(out_pts.end(), per_model[0].begin(), per_model[0].end());
     }
 
+    // A scene scale's keypoints with its float descriptors (desc, n x 128) or, desc null, its binary
+    // ones (bin_desc, n x bin_width bytes).  A binary model against a float scene (or two widths) is
+    // the library's MIM_EINVAL, thrown as mim::Error.
     struct ScaledScene {
         const std::vector<Point2f>* kp;
         const std::vector<float>* desc;
         float scale;
+        const std::vector<uint8_t>* bin_desc = nullptr;
+        int bin_width = 0;
     };
 
     // All (model, scale, view) problems of one scene in one device batch.
@@ -202,10 +212,11 @@ class Detector {
     void register_models(const std::vector<const ModelViews*>& models) {
         std::vector<RegKey> key;
         for (const ModelViews* m : models) {
-            key.push_back({m, m->identity.value(), m->views.size(), nullptr, 0, nullptr, 0, 0});
+            key.push_back({m, m->identity.value(), m->views.size(), nullptr, 0, nullptr, 0, 0, nullptr, 0, 0});
             for (const View& v : m->views)
                 key.push_back({nullptr, 0, 0, v.descriptors.data(), v.descriptors.size(),
-                               v.keypoints.empty() ? nullptr : &v.keypoints[0].x, v.keypoints.size(), sample(v)});
+                               v.keypoints.empty() ? nullptr : &v.keypoints[0].x, v.keypoints.size(), sample(v),
+                               v.bin_descriptors.data(), v.bin_descriptors.size(), v.bin_width});
         }
         int64_t gen = -1;
         check(mim_sets_info(ctx_, nullptr, &gen), "mim_sets_info", ctx_);
@@ -221,9 +232,13 @@ class Detector {
         for (size_t m = 0; m < models.size(); ++m)
             for (const View& v : models[m]->views) {
                 int32_t id;
-                check(mim_set_create(ctx_, v.descriptors.data(), v.keypoints.empty() ? nullptr : &v.keypoints[0].x,
-                                     v.size(), 128, 0, &id),
-                      "mim_set_create", ctx_);
+                const float* kp = v.keypoints.empty() ? nullptr : &v.keypoints[0].x;
+                if (v.binary())
+                    check(mim_set_create_bin(ctx_, v.bin_descriptors.data(), v.bin_width, kp, v.size(), v.bin_width, 0,
+                                             &id),
+                          "mim_set_create_bin", ctx_);
+                else
+                    check(mim_set_create(ctx_, v.descriptors.data(), kp, v.size(), 128, 0, &id), "mim_set_create", ctx_);
                 reg_ids_[m].push_back(id);
                 n = id + 1;
             }
@@ -232,7 +247,7 @@ class Detector {
         reg_n_ = n;
     }
 
-    // FNV-1a over a view's first, middle and last descriptor rows and keypoints
+    // FNV-1a over a view's first, middle and last descriptor rows (float or binary) and keypoints
     static uint64_t sample(const View& v) {
         uint64_t h = 1469598103934665603ull;
         auto mix = [&h](const void* p, size_t bytes) {
@@ -242,6 +257,9 @@ class Detector {
         const size_t n = v.keypoints.size(), rows = v.descriptors.size() / 128;
         for (size_t r : {size_t(0), rows / 2, rows ? rows - 1 : 0})
             if (r < rows) mix(&v.descriptors[r * 128], 128 * sizeof(float));
+        const size_t bw = v.bin_width > 0 ? (size_t)v.bin_width : 0, brows = bw ? v.bin_descriptors.size() / bw : 0;
+        for (size_t r : {size_t(0), brows / 2, brows ? brows - 1 : 0})
+            if (r < brows) mix(&v.bin_descriptors[r * bw], bw);
         for (size_t r : {size_t(0), n / 2, n ? n - 1 : 0})
             if (r < n) mix(&v.keypoints[r], sizeof(Point2f));
         return h;
@@ -254,9 +272,13 @@ class Detector {
         std::vector<float> sv;
         for (const ScaledScene& s : scales) {
             int32_t id;
-            check(mim_set_create(ctx_, s.desc->data(), s.kp->empty() ? nullptr : &(*s.kp)[0].x, (int32_t)s.kp->size(),
-                                 128, 0, &id),
-                  "mim_set_create", ctx_);
+            const float* kp = s.kp->empty() ? nullptr : &(*s.kp)[0].x;
+            if (!s.desc && s.bin_desc)
+                check(mim_set_create_bin(ctx_, s.bin_desc->data(), s.bin_width, kp, (int32_t)s.kp->size(), s.bin_width, 0,
+                                         &id),
+                      "mim_set_create_bin", ctx_);
+            else
+                check(mim_set_create(ctx_, s.desc->data(), kp, (int32_t)s.kp->size(), 128, 0, &id), "mim_set_create", ctx_);
             scene_ids.push_back(id);
             sv.push_back(s.scale);
         }
@@ -305,9 +327,13 @@ class Detector {
         const float* kp;
         size_t kp_size;
         uint64_t sampled;
+        const uint8_t* bin;
+        size_t bin_size;
+        int bin_width;
         bool operator==(const RegKey& o) const {
             return m == o.m && identity == o.identity && n_views == o.n_views && desc == o.desc &&
-                   desc_size == o.desc_size && kp == o.kp && kp_size == o.kp_size && sampled == o.sampled;
+                   desc_size == o.desc_size && kp == o.kp && kp_size == o.kp_size && sampled == o.sampled &&
+                   bin == o.bin && bin_size == o.bin_size && bin_width == o.bin_width;
         }
     };
     mim_ctx* ctx_ = nullptr;
