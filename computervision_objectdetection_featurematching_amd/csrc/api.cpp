@@ -161,7 +161,7 @@ struct PinnedStage {
 namespace mim {
 // RANSAC workspace (definition shared with ransac.hip through this layout)
 struct RansacWs {
-    DevBuf state, samples, hyp, counts, bounds, flags, irr_bits, irr, irr_cnt, pass_bits, defer, defer_n, chains, best_h, cand, ncand, cex, cH, decided, stream,
+    DevBuf state, samples, hyp, counts, bounds, flags, irr_bits, irr, irr_cnt, cls, cls_tab, pass_bits, defer, defer_n, chains, best_h, cand, ncand, cex, cH, decided, stream,
         scratch, inl, tiles, err;
     long long stream_len = 0;
 };
@@ -309,7 +309,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
                       &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->rws.state, &c->rws.samples,
-                      &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
+                      &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
@@ -1373,7 +1373,9 @@ static mim_status ransac_prepare(mim_ctx* c, int n, const mim_params* prm, Ransa
     mim_status s = ensure_stream(c, (long long)max_iters * 64 + 40000 * 4);
     if (s != MIM_OK) return s;
     long long it_total = 0, good_total = 0;
+    int q_max = 0;  // the largest query set bounds every problem's good-match count
     for (int i = 0; i < n; ++i) {
+        q_max = std::max(q_max, c->h_probs[i].q.n);
         it_total = std::max(it_total, c->h_probs[i].it_off + max_iters);
         good_total = std::max(good_total, c->h_probs[i].good_off + std::max(c->h_probs[i].q.n, 1));
     }
@@ -1391,6 +1393,9 @@ static mim_status ransac_prepare(mim_ctx* c, int n, const mim_params* prm, Ransa
     const int irr_blocks = (int)((flag_per + kIrrBlock - 1) / kIrrBlock);
     HIPCHK(c, c->rws.irr.ensure(sizeof(int) * (size_t)std::max(n, 1) * irr_blocks * kIrrCap));
     HIPCHK(c, c->rws.irr_cnt.ensure(sizeof(int) * (size_t)std::max(n, 1) * irr_blocks));
+    // sampler classes: one record per problem, one table slot per possible good-match count
+    HIPCHK(c, c->rws.cls.ensure(sizeof(SamplerClass) * (size_t)std::max(n, 1)));
+    HIPCHK(c, c->rws.cls_tab.ensure(sizeof(SamplerClassSlot) * ((size_t)q_max + 1)));
     HIPCHK(c, c->rws.pass_bits.ensure((size_t)flag_cap / 8));
     // deferred-attempt lists of the check rounds: a chain holds at most ~window / 4 attempts
     const int def_rounds = (int)((flag_per / 4 + 2 * kRansacDefRoundAttempts) / kRansacDefRoundAttempts);
@@ -1435,6 +1440,9 @@ static mim_status ransac_prepare(mim_ctx* c, int n, const mim_params* prm, Ransa
     const char* cde = getenv("MIM_CHECK_DEFER");
     b.def_rounds = (cde && cde[0] == '0') ? 0 : def_rounds;
     b.irr_blocks = irr_blocks;
+    b.cls = c->rws.cls.as<SamplerClass>();
+    b.cls_tab = c->rws.cls_tab.as<SamplerClassSlot>();
+    b.cls_tab_n = q_max + 1;
     b.chains = c->rws.chains.p;
     b.stream = c->rws.stream.as<uint32_t>();
     b.stream_len = c->rws.stream_len;
@@ -1479,6 +1487,7 @@ static mim_status ransac_enqueue_range(mim_ctx* c, int p0, int np, const RansacB
     g.flag_cap = (long long)np * flag_per;
     g.irr += (long long)p0 * b.irr_blocks * kIrrCap;
     g.irr_cnt += (long long)p0 * b.irr_blocks;
+    g.cls += p0;
     g.pass_bits += (long long)p0 * flag_per / 32;
     g.defer += (long long)p0 * b.def_rounds * kRansacDefSlots;
     g.defer_n += (long long)p0 * b.def_rounds;

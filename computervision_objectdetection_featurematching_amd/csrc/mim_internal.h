@@ -113,8 +113,6 @@ struct RansacState {
     int active;            // problem takes the RANSAC path (n_good > 4)
     int lo_max;            // max lower-bound count seen (filtered path: lower bound of maxGoodCount)
     unsigned long long modM;  // Lemire fast-modulo constant for % n (RNG::uniform(0, n))
-    long long win_base;    // stream position of flags[0] of the current chunk's attempt window
-    int win_len;           // attempts precomputed in that window
     float sa, sb;          // power-of-two scales of the source / destination coordinates (MFMA bound)
     float smax;            // max over points of |x|+|y|+|u|+|v| (MFMA bound margin)
     int defer;             // chunk 1's exact pass deferred to chunk 2's (no early stop possible in chunk 1)
@@ -143,6 +141,26 @@ constexpr int kRansacDefSlots = 16;             // deferred attempts listed per 
 constexpr int kRansacDefRoundAttempts = 256 * MIM_CHECK_PER;  // chain attempts per check round (kCheckBlock x kCheckPer)
 constexpr int kIrrCap = 4096;          // listed irregular attempts per block (25 %: n >= ~25 points fit)
 
+// Sampler class of one problem and chunk (ransac_class_kernel).  The attempt tables (flags, irr_bits,
+// irr, irr_cnt) are a function of (RNG stream, n, absolute stream position) only, so the windowed
+// problems of a call with equal n and nearby stream positions form a class whose leader (smallest
+// stream_pos) builds the tables once, in its own slices, at positions relative to the class base.
+struct SamplerClass {
+    long long base;  // stream position of the leader's flags[0]: the leader's stream_pos rounded down to 64
+    int leader;      // problem whose slices hold the class's tables (-1: no window this chunk)
+    int cwlen;       // positions the leader's tables cover (a multiple of 64, <= wcap)
+    int delta;       // stream_pos - base
+    int wlen;        // own window length (a multiple of 64): delta + wlen <= cwlen
+    int pad_[2];
+};
+// Slot n of the class table: key = (smallest stream_pos << 32 | that problem) over the windowed
+// problems with n points, end = largest delta + window length over the class's members.
+struct SamplerClassSlot {
+    unsigned long long key;
+    int end;
+    int pad_;
+};
+
 // Device buffers of one RANSAC batch (owned by the ctx in api.cpp).
 struct RansacBufs {
     RansacState* state;       // [n_probs]
@@ -156,8 +174,9 @@ struct RansacBufs {
     int* cex;                 // [problem][list][kCandPerProblem] their exact inlier counts
     double* cH;               // [problem][list][kCandPerProblem][9] their exact models
     int* decided;             // [problem][list][kCandPerProblem] 1: the prescreen decided the listed candidate
-    uint8_t* flags;           // [problem][window] getSubset attempt outcomes ahead of stream_pos (written and
-                              // valid only where irr_bits is set: the repeated-index and serial attempts)
+    uint8_t* flags;           // [problem][window] getSubset attempt outcomes from the class base on (written and
+                              // valid only where irr_bits is set: the repeated-index and serial attempts);
+                              // flags, irr_bits, irr and irr_cnt: only the slices of class leaders are written
     uint8_t* irr_bits;        // [problem][window / 8] bit per attempt position: irregular (its flag byte is
                               // written); a clear bit means kPassUnknown (4 draws, checkSubset not evaluated)
     long long flag_cap;       // bytes of `flags`
@@ -169,7 +188,10 @@ struct RansacBufs {
     int* defer_n;             // [problem][check round] how many are listed
     int def_rounds;           // check rounds per problem with a list (0: every deferred attempt in place)
     int irr_blocks;           // list blocks per problem
-    const uint32_t* stream;   // raw cv::RNG((uint64)-1).next() stream shared by every problem
+    SamplerClass* cls;        // [problem] sampler class of the current chunk
+    SamplerClassSlot* cls_tab;  // [cls_tab_n] class table indexed by the point count (one enqueue at a time)
+    int cls_tab_n;            // its slots: the largest query set + 1
+    const uint32_t* stream;  // raw cv::RNG((uint64)-1).next() stream shared by every problem
     long long stream_len;
     float4* inl;              // [good_off + k] compressed inliers for the refit (scratch)
     uint4* tiles;             // [good_off / 32 + tile][2][64] f16 MFMA operand tiles of the points

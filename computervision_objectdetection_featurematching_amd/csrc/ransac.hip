@@ -828,8 +828,6 @@ __device__ __forceinline__ void store_sampler_state(RansacState* d, const Ransac
     d->produced = S.produced;
     d->fail_iter = S.fail_iter;
     d->fail_run = S.fail_run;
-    d->win_base = S.win_base;
-    d->win_len = S.win_len;
 }
 __device__ __forceinline__ void store_select_state(RansacState* d, const RansacState& S) {
     d->max_good = S.max_good;
@@ -873,6 +871,79 @@ __device__ __forceinline__ int window_len(const RansacState& S, int c1, int wcap
     // measured rate: the draws of ~46k iterations vary by < 0.5 % (1 sigma), 6 % + 4096 covers them
     const long long w = (long long)((double)need * rate * (S.produced > 0 ? 1.06 : 1.25)) + 4096;
     return (int)min((long long)wcap, w) & ~63;  // whole 16-byte flag vectors and 32-bit pass words
+}
+
+// ------------------------------------------------------------------------------------------------
+// class: the chunk's windowed problems partitioned into sampler classes (SamplerClass, mim_internal.h).
+// What the attempt and irr kernels record for a stream position (do its four draws repeat an index
+// mod n, how many redraws follow) depends on the stream, n and the position only, and every problem
+// walks the same stream: problems with equal n whose positions lie within `spread` draws of the
+// smallest one share that one's tables.  One block, O(n_probs): slot n of the table takes the smallest
+// (stream_pos, problem) with atomicMin, then the largest delta + window length of the members with
+// atomicMax; a problem past the spread is a class of its own (share = 0: every problem is).
+// The state is read once, here: with the sampler stream the previous chunk's replay may lower niters
+// or set done between the sampler kernels, which all take membership, base and window lengths from
+// these records so that they agree (a problem that stopped meanwhile still leads its class).
+// ------------------------------------------------------------------------------------------------
+constexpr int kClassThreads = 1024;
+__global__ __launch_bounds__(kClassThreads) void ransac_class_kernel(const RansacState* __restrict__ st, int n_probs,
+                                                                     int c1, int wcap, int share, int spread,
+                                                                     SamplerClassSlot* __restrict__ tab, int tab_n,
+                                                                     SamplerClass* __restrict__ cls) {
+    // the slots are touched with device-scope atomics only (plain loads could hit stale L1 lines)
+    for (int p = threadIdx.x; p < n_probs; p += kClassThreads) {
+        const RansacState S = st[p];
+        const bool windowed =
+            S.active && !S.done && S.fail_iter == -1 && S.n >= kSmallMaxN && S.produced < min(c1, S.niters);
+        SamplerClass C{};
+        C.base = S.stream_pos;  // (the position itself until the last phase)
+        C.leader = windowed ? p : -1;
+        C.wlen = windowed ? window_len(S, c1, wcap) : 0;
+        C.pad_[0] = windowed && share && S.n < tab_n ? S.n : -1;  // table slot
+        cls[p] = C;
+        if (C.pad_[0] >= 0) {
+            __hip_atomic_store(&tab[S.n].key, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&tab[S.n].end, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < n_probs; p += kClassThreads) {
+        const int slot = cls[p].pad_[0];
+        if (slot >= 0) atomicMin(&tab[slot].key, ((unsigned long long)cls[p].base << 32) | (unsigned)p);
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < n_probs; p += kClassThreads) {
+        SamplerClass C = cls[p];
+        if (C.leader < 0) continue;
+        const int pos = (int)C.base, slot = C.pad_[0];
+        int lead = p, lpos = pos;
+        if (slot >= 0) {
+            const unsigned long long key = __hip_atomic_load(&tab[slot].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (pos - (int)(key >> 32) <= spread) {
+                lead = (int)(unsigned)key;
+                lpos = (int)(key >> 32);
+            } else {
+                C.pad_[0] = -1;  // past the spread: its own class
+            }
+        }
+        C.leader = lead;
+        C.delta = pos - (lpos & ~63);
+        if (C.pad_[0] >= 0) atomicMax(&tab[slot].end, C.delta + C.wlen);
+        cls[p] = C;
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < n_probs; p += kClassThreads) {
+        SamplerClass C = cls[p];
+        if (C.leader < 0) continue;
+        const int slot = C.pad_[0];
+        const int end = slot >= 0 ? __hip_atomic_load(&tab[slot].end, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                  : C.delta + C.wlen;
+        C.base = (C.base - C.delta);  // the leader's position rounded down to 64
+        C.cwlen = min(wcap, (end + 63) & ~63);
+        C.wlen = max(min(C.wlen, (C.cwlen - C.delta) & ~63), 0);
+        C.pad_[0] = 0;
+        cls[p] = C;
+    }
 }
 
 // Outcome of the getSubset attempt whose draws start at q, as one byte: bit 0 = checkSubset
@@ -973,7 +1044,8 @@ __device__ __forceinline__ void sampler_slice_block(int n_probs, int bpp, int& p
 __global__ __launch_bounds__(256) void ransac_attempt_kernel(const RansacState* __restrict__ st,
                                                              const uint32_t* __restrict__ stream, long long slen,
                                                              uint8_t* __restrict__ flags, uint8_t* __restrict__ ibits,
-                                                             int wcap, int bpp, int c1, int rep_cap, int n_probs) {
+                                                             int wcap, int bpp, int c1, int rep_cap, int n_probs,
+                                                             const SamplerClass* __restrict__ cls) {
     constexpr int D = kAttemptPerThread + 3;  // the first 4 draws of the thread's 8 attempts
     constexpr int kStageVecs = kAttemptSpan / 4 + 4;  // 16-byte vectors: the span, its 3 extra draws, alignment
     __shared__ __attribute__((aligned(16))) unsigned sdraw[4 * kStageVecs];
@@ -981,12 +1053,16 @@ __global__ __launch_bounds__(256) void ransac_attempt_kernel(const RansacState* 
     __shared__ int n_rep;
     int p, kb;
     sampler_slice_block(n_probs, bpp, p, kb);
+    // one table per class, in its leader's slices at positions relative to the class base (a multiple
+    // of 64); the blocks of the other problems have nothing to do
+    const SamplerClass C = cls[p];
+    if (C.leader != p) return;
     const RansacState S = st[p];
-    if (!S.active || S.done || S.fail_iter != -1 || S.n < kSmallMaxN || S.produced >= min(c1, S.niters)) return;
-    const int wlen = window_len(S, c1, wcap);  // a multiple of 64
+    const int wlen = C.cwlen;  // a multiple of 64
+    const int sbase = (int)C.base;
     MIM_DEBUG_PRINT(threadIdx.x == 0 && kb == 0 && (p == 0 || p == 100),
-                    "[attempt] p=%d c1=%d wlen=%d bpp=%d produced=%d stream_pos=%lld n=%d\n", p, c1, wlen, bpp, S.produced,
-                    (long long)S.stream_pos, S.n);
+                    "[attempt] p=%d c1=%d wlen=%d bpp=%d produced=%d stream_pos=%lld base=%d n=%d\n", p, c1, wlen, bpp,
+                    S.produced, (long long)S.stream_pos, sbase, S.n);
     uint8_t* __restrict__ F = flags + (long long)p * wcap;
     uint8_t* __restrict__ IB = ibits + (long long)p * (wcap >> 3);
     const unsigned N = (unsigned)S.n, mB = 0xFFFFFFFFu / N;
@@ -1003,7 +1079,7 @@ __global__ __launch_bounds__(256) void ransac_attempt_kernel(const RansacState* 
     static_assert(NV == 3, "stage vectors per thread");
 #define MIM_ATTEMPT_LOAD_STAGE(bo)                                                   \
     {                                                                                \
-        const int qv = ((int)S.stream_pos + (bo)) >> 2;                              \
+        const int qv = (sbase + (bo)) >> 2;                                          \
         v0 = sv[min(qv + min((int)threadIdx.x, kStageVecs - 1), nvec - 1)];          \
         v1 = sv[min(qv + min((int)threadIdx.x + 256, kStageVecs - 1), nvec - 1)];    \
         v2 = sv[min(qv + min((int)threadIdx.x + 512, kStageVecs - 1), nvec - 1)];    \
@@ -1014,7 +1090,7 @@ __global__ __launch_bounds__(256) void ransac_attempt_kernel(const RansacState* 
     // longer window (low checkSubset pass rate) is covered by the same blocks looping
     for (int boff = kb * kAttemptSpan; boff < wlen; boff += bpp * kAttemptSpan) {
     __syncthreads();  // the previous round's reads of sdraw are done (and n_rep's reset seen)
-    const int qb = (int)S.stream_pos + boff;
+    const int qb = sbase + boff;
     const int shift = qb & 3;
     if (!MIM_ATTEMPT_PREFETCH) MIM_ATTEMPT_LOAD_STAGE(boff);
     sd4[threadIdx.x] = v0;
@@ -1079,7 +1155,7 @@ __global__ __launch_bounds__(256) void ransac_attempt_kernel(const RansacState* 
     for (int e = threadIdx.x; e < nr; e += 256) {
         const int pos = rep_pos[e];
         int idx[4];
-        const int len = resolve_at(S.stream_pos + pos, stream, slen, N, S.modM, idx);
+        const int len = resolve_at(sbase + pos, stream, slen, N, S.modM, idx);
         F[pos] = (uint8_t)((len == 0 || len > 67) ? kAttemptSerial : (((len - 4) << 1) | kPassUnknown));
     }
 }
@@ -1135,12 +1211,12 @@ __device__ __forceinline__ int mbcnt64(unsigned long long m) {
 __global__ __launch_bounds__(256) void ransac_irr_kernel(const RansacState* __restrict__ st,
                                                          const uint8_t* __restrict__ ibits, int wcap, int bpp,
                                                          int c1, int* __restrict__ irr, int* __restrict__ irr_cnt,
-                                                         int irr_blocks) {
+                                                         int irr_blocks, const SamplerClass* __restrict__ cls) {
     __shared__ int wsum[4];
     const int p = blockIdx.x / bpp, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const RansacState S = st[p];
-    if (!S.active || S.done || S.fail_iter != -1 || S.n < kSmallMaxN || S.produced >= min(c1, S.niters)) return;
-    const int wlen = window_len(S, c1, wcap);
+    const SamplerClass C = cls[p];
+    if (C.leader != p) return;  // the class's list: once, in its leader's slices
+    const int wlen = C.cwlen;
     for (int b = blockIdx.x % bpp; b * kIrrBlock < wlen; b += bpp) {
     __syncthreads();  // wsum of the previous round read
     const int b0 = b * kIrrBlock;
@@ -1276,21 +1352,25 @@ __global__ __launch_bounds__(kWalkThreads) void ransac_walk_kernel(const RansacS
                                                                     const uint8_t* __restrict__ flags, int wcap,
                                                                     int c1, const int* __restrict__ irr,
                                                                     const int* __restrict__ irr_cnt, int irr_blocks,
-                                                                    ChainSegs* __restrict__ chains) {
+                                                                    ChainSegs* __restrict__ chains,
+                                                                    const SamplerClass* __restrict__ cls) {
     __shared__ ChainWalkShared sh;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const RansacState S = st[p];
+    const SamplerClass C = cls[p];
     ChainSegs* G = chains + p;
-    if (!S.active || S.done || S.fail_iter != -1 || S.n < kSmallMaxN || S.produced >= min(c1, S.niters)) {
+    if (C.leader < 0) {
         if (tid == 0) G->T = -1;  // nothing to do this chunk (small problems: ransac_small_kernel)
         return;
     }
-    const int wlen = window_len(S, c1, wcap);
-    const uint8_t* F = flags + (long long)p * wcap;
+    // positions are relative to the class base; the problem's own walk covers [delta, delta + wlen) of
+    // its leader's tables
+    const int wlen = C.delta + C.wlen;
+    const int pl = C.leader;
+    const uint8_t* F = flags + (long long)pl * wcap;
     const int nb = min((wlen + kIrrBlock - 1) / kIrrBlock, kIrrBlocksMax);
     // the listed blocks up to the first overflowing one (more than kIrrCap irregular positions)
     {
-        const int cnt = tid < nb ? irr_cnt[(long long)p * irr_blocks + tid] : 0;
+        const int cnt = tid < nb ? irr_cnt[(long long)pl * irr_blocks + tid] : 0;
         const int bad = tid < nb && cnt < 0 ? tid : INT_MAX;
         int total;
         const int off = block_excl_sum(max(cnt, 0), sh.wred, total);
@@ -1299,7 +1379,7 @@ __global__ __launch_bounds__(kWalkThreads) void ransac_walk_kernel(const RansacS
         __syncthreads();
         if (tid == 0) {
             sh.cut = cut;
-            sh.n_entries = cut > 0 ? sh.boff[cut - 1] + irr_cnt[(long long)p * irr_blocks + cut - 1] : 0;
+            sh.n_entries = cut > 0 ? sh.boff[cut - 1] + irr_cnt[(long long)pl * irr_blocks + cut - 1] : 0;
             sh.limit = min(wlen, cut * kIrrBlock);
             sh.stop = 0;
         }
@@ -1307,7 +1387,7 @@ __global__ __launch_bounds__(kWalkThreads) void ransac_walk_kernel(const RansacS
     }
     // the entries stream through LDS in pieces of kChainEntries; wave 0 walks each piece, keeping its
     // chain position across pieces (entries are in ascending position order)
-    int s = 0, nwalk = 0, limit = sh.limit;
+    int s = C.delta, nwalk = 0, limit = sh.limit;
     const int E = sh.n_entries, cut = sh.cut;
     for (int eb = 0; eb < E; eb += kChainEntries) {
         const int ee = min(E, eb + kChainEntries);
@@ -1317,7 +1397,7 @@ __global__ __launch_bounds__(kWalkThreads) void ransac_walk_kernel(const RansacS
                 const int mid = (lo + hi + 1) >> 1;
                 if (sh.boff[mid] <= e) lo = mid; else hi = mid - 1;
             }
-            const int q = irr[((long long)p * irr_blocks + lo) * kIrrCap + (e - sh.boff[lo])];
+            const int q = irr[((long long)pl * irr_blocks + lo) * kIrrCap + (e - sh.boff[lo])];
             sh.q[e - eb] = q;
             sh.f[e - eb] = F[q];
         }
@@ -1362,7 +1442,7 @@ __global__ __launch_bounds__(kWalkThreads) void ransac_walk_kernel(const RansacS
             G->nseg = nwalk;
             G->tail = tail;
             G->s_end = s + 4 * tail;
-            G->wbase = S.stream_pos;
+            G->wbase = C.base;
             G->wlen = wlen;
         }
     }
@@ -1659,7 +1739,8 @@ __global__ __launch_bounds__(kChainThreads) void ransac_count_kernel(RansacState
                                                                      const ChainSegs* __restrict__ chains,
                                                                      const uint32_t* __restrict__ pass_bits,
                                                                      const uint8_t* __restrict__ flags, int wcap,
-                                                                     int4* __restrict__ samples, int c1) {
+                                                                     int4* __restrict__ samples, int c1,
+                                                                     const SamplerClass* __restrict__ cls) {
     __shared__ ChainCountShared sh;
     const int p = blockIdx.x, tid = threadIdx.x;
     const ChainSegs* G = chains + p;
@@ -1736,8 +1817,6 @@ __global__ __launch_bounds__(kChainThreads) void ransac_count_kernel(RansacState
         });
     }
     if (tid == 0) {
-        S.win_base = wbase;
-        S.win_len = G->wlen;
         if (t_fail < t_need) {
             S.produced += keep;
             S.fail_iter = S.produced;  // getSubset returned false in this iteration
@@ -1746,7 +1825,7 @@ __global__ __launch_bounds__(kChainThreads) void ransac_count_kernel(RansacState
             const int j = chain_seg(G, t_need);
             bool irregular;
             const int pos = chain_pos(G, j, t_need, irregular);
-            const int len = irregular ? 4 + ((flags[(long long)p * wcap + pos] & 0x7F) >> 1) : 4;
+            const int len = irregular ? 4 + ((flags[(long long)cls[p].leader * wcap + pos] & 0x7F) >> 1) : 4;
             S.produced = target;
             S.stream_pos = wbase + pos + len;
             S.fail_run = 0;
@@ -2118,7 +2197,8 @@ __global__ __launch_bounds__(64) void ransac_sample_kernel(RansacState* __restri
                                                            const uint32_t* __restrict__ stream, long long slen,
                                                            int4* __restrict__ samples, int c1,
                                                            int* __restrict__ err, const uint8_t* __restrict__ flags,
-                                                           const uint8_t* __restrict__ ibits, int wcap, int after_chain) {
+                                                           const uint8_t* __restrict__ ibits, int wcap,
+                                                           const SamplerClass* __restrict__ cls) {
     __shared__ __attribute__((aligned(16))) uint8_t win[kFlagWin];
     constexpr int BIG = 1 << 30;
     const int p = blockIdx.x, lane = threadIdx.x;
@@ -2126,11 +2206,15 @@ __global__ __launch_bounds__(64) void ransac_sample_kernel(RansacState* __restri
     if (!S.active || S.done || S.fail_iter != -1 || S.n < kSmallMaxN) return;  // small: ransac_small_kernel
     const int target = min(c1, S.niters);
     if (S.produced >= target) return;
-    // resume where ransac_chain_kernel stopped; flags[rel] is the attempt starting at wbase + rel
-    const long long wbase = after_chain ? S.win_base : S.stream_pos;
-    const int wlen = after_chain ? S.win_len : window_len(S, c1, wcap);
-    const uint8_t* F = flags + (long long)p * wcap;
-    const uint8_t* IB = ibits + (long long)p * (wcap >> 3);
+    // resume where the chain kernels stopped; flags[rel] is the attempt starting at wbase + rel, in the
+    // slices of the class's leader, valid up to the end of the problem's own window (a problem that
+    // passes the guard above had a window when the class kernel ran: niters only falls)
+    const SamplerClass C = cls[p];
+    const int pl = max(C.leader, 0);
+    const long long wbase = C.leader >= 0 ? C.base : S.stream_pos;
+    const int wlen = C.leader >= 0 ? C.delta + C.wlen : 0;
+    const uint8_t* F = flags + (long long)pl * wcap;
+    const uint8_t* IB = ibits + (long long)pl * (wcap >> 3);
     const unsigned N = (unsigned)S.n;
     const unsigned long long M = S.modM;
     const float4* P = pts + probs[p].good_off;
@@ -4077,6 +4161,12 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
     // the sampler grids' floor (MIM_SAMPLER_MIN_BLOCKS: blocks in all; 0 = only what the window needs)
     int min_blocks = kSamplerMinBlocks;
     if (const char* mb = getenv("MIM_SAMPLER_MIN_BLOCKS")) min_blocks = std::max(0, atoi(mb));
+    // sampler classes (ransac_class_kernel).  MIM_SAMPLER_SHARE=0: every problem its own class;
+    // MIM_SHARE_SPREAD=<draws>: how far past the class's smallest stream position a member may start
+    // (default 1/16 of the window capacity: a typical window fills ~0.8 of it, so delta + wlen still fits)
+    const char* she = getenv("MIM_SAMPLER_SHARE");
+    const int share = (she && she[0] == '0') ? 0 : 1;
+    const char* spe = getenv("MIM_SHARE_SPREAD");
     while (c0 < max_iters) {
         const int c1 = (int)std::min<long long>((long long)c0 + chunk, max_iters);
         // attempt outcomes for a window of ~28 draws per wanted iteration (pass rate ~1/5), the walk
@@ -4092,16 +4182,36 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
                                    std::min(bppw_cap, (min_blocks + n_probs - 1) / n_probs)) + 7) / 8 * 8;
         // (MIM_ATTEMPT_REP_CAP < kAttemptRepCap: test knob forcing the in-place redraw resolution)
         const int rep_cap = prm.rep_cap > 0 ? std::min(prm.rep_cap, kAttemptRepCap) : kAttemptRepCap;
+        const int spread = std::min(spe ? std::max(0, atoi(spe)) : wcap / 16, wcap / 2);
+        // debug (MIM_DEBUG_NCLASS): the chunk's windowed problems and classes, with host syncs.  The
+        // sampler stream runs ahead of the previous chunk's selection, so which stopped problems the class
+        // kernel still sees as live depends on timing (the results do not); the debug line waits for the
+        // selection first, so that its counts are those of the finished previous chunk
+        const bool dbg_ncls = getenv("MIM_DEBUG_NCLASS") != nullptr;
+        if (dbg_ncls && split) (void)hipStreamSynchronize(s);
+        ransac_class_kernel<<<1, kClassThreads, 0, ss>>>(b.state, n_probs, c1, wcap, share, spread, b.cls_tab,
+                                                         b.cls_tab_n, b.cls);
+        if (dbg_ncls) {
+            std::vector<SamplerClass> hc(n_probs);
+            (void)hipMemcpyAsync(hc.data(), b.cls, sizeof(SamplerClass) * n_probs, hipMemcpyDeviceToHost, ss);
+            (void)hipStreamSynchronize(ss);
+            int nw = 0, nc = 0;
+            for (int i = 0; i < n_probs; ++i) {
+                nw += hc[i].leader >= 0;
+                nc += hc[i].leader == i;
+            }
+            fprintf(stderr, "[mim] sampler chunk [%d,%d): windowed %d classes %d\n", c0, c1, nw, nc);
+        }
         ransac_attempt_kernel<<<n_probs * bppw, 256, 0, ss>>>(b.state, b.stream, b.stream_len, b.flags, b.irr_bits, wcap,
-                                                             bppw, c1, rep_cap, n_probs);
+                                                             bppw, c1, rep_cap, n_probs, b.cls);
         mark(mark_ctx, "attempt", ss);
         if (use_chain) {
             ChainSegs* chains = reinterpret_cast<ChainSegs*>(b.chains);
             const int bpp_irr = (west + kIrrBlock - 1) / kIrrBlock;
             ransac_irr_kernel<<<n_probs * bpp_irr, 256, 0, ss>>>(b.state, b.irr_bits, wcap, bpp_irr, c1, b.irr,
-                                                               b.irr_cnt, b.irr_blocks);
+                                                               b.irr_cnt, b.irr_blocks, b.cls);
             ransac_walk_kernel<<<n_probs, kWalkThreads, 0, ss>>>(b.state, b.flags, wcap, c1, b.irr, b.irr_cnt,
-                                                                 b.irr_blocks, chains);
+                                                                 b.irr_blocks, chains, b.cls);
             mark(mark_ctx, "chain", ss);
             constexpr int kChkSpan = kCheckBlock * kCheckPer;
             const int bpp_chk = std::max((west / 4 + kChkSpan) / kChkSpan,  // T ~ wlen / 4
@@ -4117,13 +4227,13 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
             }
             mark(mark_ctx, "check", ss);
             ransac_count_kernel<<<n_probs, kChainThreads, 0, ss>>>(b.state, probs, chains, b.pass_bits, b.flags, wcap,
-                                                                  b.samples, c1);
+                                                                  b.samples, c1, b.cls);
             mark(mark_ctx, "chain", ss);
         }
         ransac_small_kernel<<<n_probs, kSmallThreads, 0, ss>>>(b.state, probs, pts, b.stream, b.stream_len, b.samples,
                                                               c1, b.err);
         ransac_sample_kernel<<<n_probs, 64, 0, ss>>>(b.state, probs, pts, b.stream, b.stream_len, b.samples, c1, b.err,
-                                                    b.flags, b.irr_bits, wcap, use_chain);
+                                                    b.flags, b.irr_bits, wcap, b.cls);
         mark(mark_ctx, "sample", ss);
         if (split) {  // this chunk's selection waits for its samples; the next chunk's sampler does not
             (void)hipEventRecord(b.ev_samp[ci & 1], ss);
