@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +26,7 @@
 namespace mim {
 void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStream_t st);
 void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const int* seg_start, int n_blocks, Top2* parts,
-                int* dyn_ctr, hipStream_t st);
+                int* dyn_ctr, float kappa, hipStream_t st);
 int knn_blocks_per_cu();
 void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
 void launch_ratio(const ProbDev* probs, int n_probs, const Top2* parts, float ratio, int32_t* good_q,
@@ -902,10 +903,22 @@ static void ev_collect(mim_ctx* c) {
     c->evs.clear();
 }
 
-static void knn_launch(mim_ctx* c) {
+// kappa of the distance kernel's ratio mode (knn.hip): ratio^2 (1 + 2^-18) covers the three float
+// roundings of sqrtf(d1) < ratio * sqrtf(d2), a further 2^-20 and the round-up the kernel's own float
+// product.  0 = exact top-2: ratios whose kappa is not below 1, and MIM_KNN_RATIO=0 (read per launch).
+static float knn_ratio_kappa(float ratio) {
+    const char* e = getenv("MIM_KNN_RATIO");
+    if (e && e[0] == '0') return 0.f;
+    if (!(ratio > 0.f && ratio < 1.f)) return 0.f;
+    const double k = (double)ratio * (double)ratio * (1.0 + 1.0 / 262144.0) * (1.0 + 1.0 / 1048576.0);
+    const float kf = nextafterf((float)k, 2.f);
+    return kf < 1.f ? kf : 0.f;
+}
+
+static void knn_launch(mim_ctx* c, float kappa = 0.f) {
     const KnnWork* w = c->works.as<KnnWork>();
     launch_knn(c->probs.as<ProbDev>(), w, c->n_works, reinterpret_cast<const int*>(w + c->n_works), c->n_knn_blocks,
-               c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, c->cur);
+               c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, kappa, c->cur);
     launch_knn_hamming(c->ham_works.as<HamWork>(), c->n_ham_works, c->cur);
 }
 
@@ -913,7 +926,8 @@ static void knn_launch(mim_ctx* c) {
 static mim_status knn_ratio_locked(mim_ctx* c, int n, float ratio, bool emit_knn) {
     c->cur = c->stream;
     ev_mark(c, "begin");
-    knn_launch(c);
+    // the ratio test is the only reader of the top-2 unless the knnMatch rows are emitted
+    knn_launch(c, emit_knn ? 0.f : knn_ratio_kappa(ratio));
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "knn");
     launch_ratio(c->probs.as<ProbDev>(), n, c->parts.as<Top2>(), ratio, c->good_q.as<int32_t>(), c->good_t.as<int32_t>(),

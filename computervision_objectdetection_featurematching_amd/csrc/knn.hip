@@ -148,6 +148,26 @@ __device__ __forceinline__ LaneSel sel_merge(LaneSel a, const LaneSel& b) {
     return a;
 }
 
+// Ratio mode (knn2_i8_kernel<true>): the two smallest D as values and the index of the smallest
+// only.  Which of two equal minima gives i1 does not matter: a query whose two smallest are equal
+// fails every ratio test below 1.
+__device__ __forceinline__ void sel_push_r(LaneSel& s, int v, int idx) {
+    const bool c1 = v < s.m1;
+    s.m2 = max(min(s.m1, s.m2), min(max(s.m1, s.m2), v));
+    s.m1 = min(s.m1, v);
+    s.i1 = c1 ? idx : s.i1;
+}
+
+__device__ __forceinline__ LaneSel sel_merge_r(const LaneSel& a, const LaneSel& b) {
+    LaneSel r;
+    const bool l = b.m1 < a.m1;
+    r.m1 = l ? b.m1 : a.m1;
+    r.i1 = l ? b.i1 : a.i1;
+    r.m2 = min(max(a.m1, b.m1), min(a.m2, b.m2));  // 2nd smallest of {a.m1 <= a.m2, b.m1 <= b.m2}
+    r.i2 = INT_MAX;
+    return r;
+}
+
 __device__ __forceinline__ bool key_less(float ka, int ia, float kb, int ib) {
     return ka < kb || (ka == kb && ia < ib);
 }
@@ -207,6 +227,13 @@ constexpr int kEarlyTiles = MIM_KNN_EARLY;
 __device__ __forceinline__ int late_threshold(const LaneSel& s, int o1, int o2) {
     return min(max(s.m1, o1), min(s.m2, o2)) >> 1;  // 2nd smallest of {m1 <= m2, o1 <= o2}, halved
 }
+// Ratio mode: 1st and 2nd smallest of the lane pair's four D (partner copy o1 <= o2, stale = larger)
+__device__ __forceinline__ int pair_first(const LaneSel& s, int o1) { return min(s.m1, o1); }
+__device__ __forceinline__ int pair_second(const LaneSel& s, int o1, int o2) {
+    return min(max(s.m1, o1), min(s.m2, o2));
+}
+// rows with D < v: D = 2R + p <= v - 1 gives R <= floor((v - 1) / 2)
+__device__ __forceinline__ int below_threshold(int v) { return (v - 1) >> 1; }
 __device__ __forceinline__ int dval(int R, int p) { return (R << 1) | p; }  // v_lshl_or_b32
 
 // v_med3_u32 (the compiler rewrites the max/min form of a top-2 update into a max and two mins)
@@ -251,11 +278,35 @@ static_assert(kStageChunks * 16 * kThreads == kStage * kTileBytes, "stage split"
 #ifndef MIM_KNN_OCC
 #define MIM_KNN_OCC 4
 #endif
+//
+// Ratio mode (RATIO, kappa in (0, 1)): the batch path reads the top-2 only through the ratio test
+// k1 < ratio * k2 and i1 where it passes, so a lane pair that fails the test needs less than its exact
+// 2nd neighbour.  kappa >= ratio^2 (1 + 2^-18): d1^2 >= kappa d2^2 makes the float test false, and a
+// smaller d2^2 keeps it false.  Q1 <= Q2 are the two smallest of the pair's four list values, G1 <= G2
+// the two smallest D of all rows so far.  Invariant: Q1 = G1, Q2 >= G2, and Q2 = G2 or F(Q1, Q2), where
+// F(a, b) is the float test (a + c) >= kappa (b + c), monotone in b.  A refresh sets a lane's limit to
+// v = Q1 when F(Q1, Q2) holds (failing), else v = Q2 (candidate); a row with D >= v is ignored.
+//   Inserting a row keeps the invariant: Q1, Q2 become the two smallest of {Q1, Q2, D}; with Q2 > G2
+//   and D < Q1 the new second is the old G1, exact again; with Q1 <= D < Q2, F(Q1, D) follows from F(Q1, Q2).
+//   Ignoring a row under a candidate limit (D >= Q2 >= G2) changes nothing.
+//   Ignoring a row under a failing limit v = Q1r (the refresh's pair Q1r, Q2r, F(Q1r, Q2r)): while Q1 is
+//   still Q1r, D >= G1 can only lower G2, and F(Q1r, Q2) holds as Q2 <= Q2r; once an insertion has lowered
+//   Q1, Q2 <= Q1r <= D and the row changes nothing.  Partner values are stale, that is larger: limits only
+//   grow.  After an insertion the limit becomes min(limit, candidate limit of the fresh pair): for a
+//   failing lane that is a change only when Q1 fell, and then Q2 <= Q1r.
+// So a failing pair takes an event only for a new minimum, not for every row that enters its top-2.
+// At the end the split emits (Q1, i1, Q2): exact, or failing with Q2 too large, which fails the test as
+// the true pair does; merged with other splits' pairs the same invariant holds (the minimum is exact,
+// the second too large only behind F).  Equal minima fail the test, so i1 and the rescan's index order do
+// not matter.  Thresholds are on R: D < v is R <= floor((v - 1) / 2).
+template <bool RATIO>
 __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC = waves per SIMD
     const ProbDev* __restrict__ probs, const KnnWork* __restrict__ works, const int* __restrict__ seg_start,
-    Top2* __restrict__ parts, int* __restrict__ dyn_ctr) {
+    Top2* __restrict__ parts, int* __restrict__ dyn_ctr, float kappa) {
     constexpr int QT = kKnnQT;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * kStage * kLdsTile];
+    // ratio mode: c(q) of the work item's queries behind the two stage buffers (read once per stage)
+    constexpr int kCqOff = 2 * kStage * kLdsTile;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kCqOff + (RATIO ? 4 * kKnnBlockQ : 0)];
     __shared__ int s_item;
     // static: block b runs works[seg_start[b] .. seg_start[b + 1]); dynamic (dyn_ctr != null): the works
     // are 8 lists (seg_start[0..8]), block b pulls items from list b mod 8 (its XCD's) with an atomic
@@ -311,11 +362,30 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
     // insertion recomputes the threshold from its own fresh pair and these (the partner's values only
     // decrease, so a stale copy gives a threshold >= the exact one: a superset, no exchange per event)
     int o1c[QT], o2c[QT];
+    const int* cq = reinterpret_cast<const int*>(smem + kCqOff) + wave * 32 * QT + r;  // ratio mode
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
         sel_init(st[u]);
         T[u] = INT_MAX;
     }
+    if (RATIO) {
+        // (the previous work item's last read of these words lies before its last stage barrier)
+        for (int k = tid; k < kKnnBlockQ; k += kThreads) {
+            const int q = w.q0 + k, qt = q >> 6;
+            const int qtc = qt < P->q.n_tiles ? qt : 0;  // as the fragments: never written out
+            reinterpret_cast<int*>(smem + kCqOff)[k] = ((const gint*)P->q.norm)[(size_t)qtc * kNormWords + 128 + (q & 63)];
+        }
+    }
+    // threshold after an insertion.  Ratio mode: never above the one set at the last refresh (a
+    // failing pair keeps its lower threshold through other lanes' events, see the proof above)
+    auto event_threshold = [&](int u) {
+        if (RATIO) T[u] = min(T[u], below_threshold(pair_second(st[u], o1c[u], o2c[u])));
+        else T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+    };
+    auto push = [&](int u, int v, int idx) {
+        if (RATIO) sel_push_r(st[u], v, idx);
+        else sel_push(st[u], v, idx);
+    };
 
     // ---- staging: LDS-DMA (global_load_lds_dwordx4 / _dword), double buffered, one barrier per
     // stage of kStage 64-row tiles.  One wave-instruction writes 64 lanes x size contiguous bytes at a
@@ -416,8 +486,8 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
             t.m1 = k1[u] == 0xFFFFFFFFu ? INT_MAX : (int)(k1[u] - (1u << 28)) >> 7;
             t.i1 = k1[u] == 0xFFFFFFFFu ? INT_MAX : tile * 64 + (int)(k1[u] & 127) - 4 * h;
             t.m2 = k2[u] == 0xFFFFFFFFu ? INT_MAX : (int)(k2[u] - (1u << 28)) >> 7;
-            t.i2 = k2[u] == 0xFFFFFFFFu ? INT_MAX : tile * 64 + (int)(k2[u] & 127) - 4 * h;
-            st[u] = sel_merge(st[u], t);
+            t.i2 = RATIO || k2[u] == 0xFFFFFFFFu ? INT_MAX : tile * 64 + (int)(k2[u] & 127) - 4 * h;
+            st[u] = RATIO ? sel_merge_r(st[u], t) : sel_merge(st[u], t);
         }
     };
     // late tiles: one min over a lane's 16 R per column tile against its threshold, the exact
@@ -476,12 +546,12 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                                     k1 = min(k1, key);
                                 }
                                 const int pos1 = (k1 & 3) + 8 * ((k1 >> 2) & 1) + 16 * i;
-                                sel_push(st[u], dval(k1 >> 3, (pw >> pos1) & 1), row0 + pos1);
-                                T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+                                push(u, dval(k1 >> 3, (pw >> pos1) & 1), row0 + pos1);
+                                event_threshold(u);
                                 if (__builtin_expect(__ballot((k2 >> 3) <= T[u]) == 0, 1)) continue;
                                 const int pos2 = (k2 & 3) + 8 * ((k2 >> 2) & 1) + 16 * i;
-                                sel_push(st[u], dval(k2 >> 3, (pw >> pos2) & 1), row0 + pos2);
-                                T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+                                push(u, dval(k2 >> 3, (pw >> pos2) & 1), row0 + pos2);
+                                event_threshold(u);
                             }
                             // rows in index order (keyed: only those after the second key, all of which
                             // have a larger D than the two pushed rows' or an equal D and a larger row)
@@ -493,12 +563,12 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
 #pragma unroll
                             for (int g = 8 * i; g < 8 * i + 8; ++g) {
                                 if (__builtin_expect(hm[g - 8 * i] != 0, 0))
-                                    sel_push(st[u], dval(acc[u][g], (pw >> ((g & 3) + 8 * (g >> 2))) & 1),
-                                             row0 + (g & 3) + 8 * (g >> 2));
+                                    push(u, dval(acc[u][g], (pw >> ((g & 3) + 8 * (g >> 2))) & 1),
+                                         row0 + (g & 3) + 8 * (g >> 2));
                             }
                         }
                     }
-                    T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+                    event_threshold(u);
                 }
             }
         }
@@ -561,6 +631,11 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
     for (; stage < w.tile1; stage += kStage) {
         const int buf = ((stage - w.tile0) / kStage) & 1;
         const bool more = stage + kStage < w.tile1;
+        // c(q) for the refresh, read before the next stage's DMA is issued: an LDS read after it
+        // would wait for that DMA (the waitcnt pass cannot tell the words apart)
+        int cqv[QT];
+#pragma unroll
+        for (int u = 0; u < QT; ++u) cqv[u] = RATIO ? cq[32 * u] : 0;
         if (more) stage_dma(stage + kStage, buf ^ 1, false);
         const unsigned char* sb = smem + buf * kStage * kLdsTile;
         flush_deferred();  // the previous stage's last half tile (waves 4-7 with MIM_KNN_STAGGER)
@@ -571,7 +646,15 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                 const auto b = __builtin_amdgcn_permlane32_swap(st[u].m2, st[u].m2, false, false);
                 o1c[u] = (tid & 32) ? (int)a[0] : (int)a[1];
                 o2c[u] = (tid & 32) ? (int)b[0] : (int)b[1];
-                T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+                if (RATIO) {
+                    // the pair's two smallest D, both halves fresh: exact or failing (invariant above)
+                    const int q1 = pair_first(st[u], o1c[u]), q2 = pair_second(st[u], o1c[u], o2c[u]);
+                    const int c = cqv[u];
+                    const bool fail = q2 != INT_MAX && (float)(q1 + c) >= kappa * (float)(q2 + c);
+                    T[u] = below_threshold(fail ? q1 : q2);
+                } else {
+                    T[u] = late_threshold(st[u], o1c[u], o2c[u]);
+                }
             }
         };
         refresh();
@@ -590,11 +673,16 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
     for (int u = 0; u < QT; ++u) {
         LaneSel m = st[u];
         if (m.i1 != INT_MAX) m.i1 += 4 * h;
-        if (m.i2 != INT_MAX) m.i2 += 4 * h;
+        if (!RATIO && m.i2 != INT_MAX) m.i2 += 4 * h;
         LaneSel o;
         o.m1 = __shfl_xor(m.m1, 32); o.m2 = __shfl_xor(m.m2, 32);
-        o.i1 = __shfl_xor(m.i1, 32); o.i2 = __shfl_xor(m.i2, 32);
-        m = sel_merge(m, o);
+        o.i1 = __shfl_xor(m.i1, 32); o.i2 = RATIO ? INT_MAX : __shfl_xor(m.i2, 32);
+        if (RATIO) {
+            m = sel_merge_r(m, o);
+            m.i2 = m.m2 == INT_MAX ? INT_MAX : m.i1;  // any valid index: only k2 is read downstream
+        } else {
+            m = sel_merge(m, o);
+        }
         const int q = qbase + 32 * u + r;
         if (h == 0 && q < nq) {
             // c(q), read here rather than held in a register for the whole sweep
@@ -607,7 +695,9 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
             t.i2 = m.i2;
             // d^2 >= 4e6: distinct integers may share a key (sqrt class), where the lower index
             // wins: rescan exactly.  Below, equal keys mean equal d^2, already in index order.
-            if (t.i2 != INT_MAX && d2 >= 4000000) t.i2 = kRescan;
+            // (ratio mode: the test reads the two smallest keys as values, and those are the keys of
+            // the two smallest d^2 in any sqrt class: no rescan)
+            if (!RATIO && t.i2 != INT_MAX && d2 >= 4000000) t.i2 = kRescan;
             parts[P->part_off + (long long)w.split * P->q_pad + q] = t;
         }
     }
@@ -885,16 +975,22 @@ void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStrea
 // device) and only the matching kernel does the work, so no host round trip is needed.
 int knn_blocks_per_cu() {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, knn2_i8_kernel, kThreads, 0) != hipSuccess) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, knn2_i8_kernel<false>, kThreads, 0) != hipSuccess) nb = 1;
     return nb;
 }
 
 void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const int* seg_start, int n_blocks,
-                Top2* parts, int* dyn_ctr, hipStream_t st) {
+                Top2* parts, int* dyn_ctr, float kappa, hipStream_t st) {
     if (n_works <= 0) return;
     if (dyn_ctr) (void)hipMemsetAsync(dyn_ctr, 0, 8 * sizeof(int), st);
-    knn2_i8_kernel<<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr);
-    knn2_rescan_kernel<<<n_works, 256, 0, st>>>(probs, works, parts);
+    // kappa in (0, 1): the ratio-mode instantiation (its parts feed ratio_compact_kernel only and
+    // mark nothing for the rescan); otherwise the exact top-2
+    if (kappa > 0.f && kappa < 1.f) {
+        knn2_i8_kernel<true><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, kappa);
+    } else {
+        knn2_i8_kernel<false><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, 0.f);
+        knn2_rescan_kernel<<<n_works, 256, 0, st>>>(probs, works, parts);
+    }
     knn2_f32_kernel<<<std::min(n_works, 2048), 256, 0, st>>>(probs, works, parts, n_works);
 }
 
