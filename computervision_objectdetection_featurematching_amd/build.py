@@ -34,8 +34,8 @@ def needs_build() -> bool:
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    deps = sources() + [os.path.join(CSRC, "mim_internal.h"), os.path.join(CSRC, "mim_debug.h"),
-                        os.path.join(HERE, "..", "include", "mim.h")]
+    deps = sources() + [os.path.join(CSRC, "mim_internal.h"), os.path.join(CSRC, "knn_schedule.h"),
+                        os.path.join(CSRC, "mim_debug.h"), os.path.join(HERE, "..", "include", "mim.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

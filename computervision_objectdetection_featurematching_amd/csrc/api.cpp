@@ -590,9 +590,19 @@ mim_status mim_set_rows(mim_ctx* c, int32_t set_id, int32_t cap, float* desc, fl
 
 }  // extern "C"
 
+// the distance schedule's knobs (knn_schedule.h), read per batch (tests switch them)
+static KnnSchedKnobs knn_knobs() {
+    KnnSchedKnobs k;
+    if (const char* e = getenv("MIM_KNN_SUB")) k.sub_target = atoi(e);
+    if (const char* e = getenv("MIM_KNN_DYN")) k.dyn = atoi(e) != 0;
+    if (const char* e = getenv("MIM_KNN_TAIL")) k.tail = atoi(e) != 0;
+    return k;
+}
+
 // ---------------------------------------------------------------------------------------------
-// Problem table + distance work list.  Work items of one problem are placed at block indices
-// with equal (index % 8) so they share one XCD's L2 under round-robin dispatch (speed only).
+// Problem table + distance work list (knn_schedule.h).  Work items of one problem are placed at
+// block indices with equal (index % 8) so they share one XCD's L2 under round-robin dispatch
+// (speed only).
 // ---------------------------------------------------------------------------------------------
 static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, int max_iters) {
     mim_status fs = flush_preps(c);  // the sets' device tiles and flags, before ProbDev copies them
@@ -603,12 +613,7 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         c->knn_grid = std::max(1, prop.multiProcessorCount * std::max(1, knn_blocks_per_cu()));
         c->n_cu = std::max(1, prop.multiProcessorCount);
     }
-    c->h_probs.assign(n, ProbDev{});
-    long long part = 0, good = 0, it = 0, units = 0;
-    // binary problems (both sets binary, one width) are known here, on the host: they stay out of the
-    // i8 schedule below and get the Hamming work list after it
-    std::vector<char> bin(n, 0);
-    long long ham_qb = 0;  // their query blocks
+    std::vector<KnnSchedProblem> in(n);
     for (int i = 0; i < n; ++i) {
         const int qs = problems[i].query_set, ts = problems[i].train_set;
         if (qs < 0 || qs >= (int)c->sets.size() || ts < 0 || ts >= (int)c->sets.size())
@@ -623,217 +628,36 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         if (Q.bin_width != T.bin_width)
             return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
                         T.bin_width);
-        if (Q.bin_pad) {
-            bin[i] = 1;
-            ham_qb += (Q.d.n + kHamBlockQ - 1) / kHamBlockQ;
-            continue;
-        }
-        units += (long long)((c->sets[qs].d.n + kKnnBlockQ - 1) / kKnnBlockQ) * c->sets[ts].d.n_tiles;
+        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
     }
-    // Balanced distance schedule.  The (problem, query block, train tile) units are cut into equal
-    // sub-chunks, every resident block of the single wave of blocks doing the same number of tiles
-    // (no tail wave).  A query block cut into k pieces gets k train splits (partial top-2 lists merged
-    // by the ratio kernel); a problem's split count is the largest over its query blocks, and the
-    // missing splits of the others are empty work items (sentinel lists).
-    // L2 locality (MIM_KNN_SUB = s > 0, tiles): with the chunk of a block longer than s, the block
-    // does R = ceil(chunk / s) sub-chunks of ~s tiles in rounds, and a problem's train tiles are
-    // ordered in segments of <= s tiles (units: problem, segment, query block, tile), so the blocks
-    // running at one time on an XCD sweep the same few segments of the same one or two problems.
-    // Placement: workgroups are dispatched round-robin over the 8 XCDs (block b on XCD b % 8), and
-    // XCD x gets the x-th eighth of the sub-chunks.  MIM_KNN_SUB = 0: segments of <= chunk tiles, one
-    // round; < 0: whole query-block sweeps, one round.
-    const char* sub_env = getenv("MIM_KNN_SUB");  // read per batch (tests switch it)
-    const int sub_target = sub_env ? atoi(sub_env) : kKnnSubTiles;
-    // Dynamic mode (whole sweeps pulled from per-XCD lists) when the batch has at least one query-block
-    // sweep per resident block: fewer pieces (no early tiles and prologue per split) and a block that
-    // starts late under other batches' kernels takes less (measured: C3 isolated kNN 1.39 -> 1.32 ms,
-    // pipelined C3 +2.5 %, 32-problem shards +3.8 %, C4 even; profiles/r03_knn_variants.txt, r03ac).
-    // Fewer sweeps than blocks (C5's one problem, a scene's small views): the static balanced chunks.
-    // MIM_KNN_DYN=0 / 1 forces either.
-    long long n_sweeps = 0;
-    for (int i = 0; i < n; ++i)
-        if (!bin[i]) n_sweeps += (c->sets[problems[i].query_set].d.n + kKnnBlockQ - 1) / kKnnBlockQ;
-    const char* dyn_env = getenv("MIM_KNN_DYN");
-    const bool dyn = dyn_env ? atoi(dyn_env) != 0 : n_sweeps >= c->knn_grid;
-    const long long G = c->knn_grid;
-    const long long chunk = std::max<long long>(kKnnMinChunk, (units + G - 1) / G);
-    const long long R = (sub_target > 0 && chunk > sub_target) ? (chunk + sub_target - 1) / sub_target : 1;
-    const long long sub = std::max<long long>(kKnnMinChunk, (chunk + R - 1) / R);
-    const long long NS = std::max<long long>(1, (units + sub - 1) / sub);  // sub-chunks
-    const long long per_x = (NS + 7) / 8;
-    const int m = (int)std::max<long long>(1, (per_x + R - 1) / R);  // blocks per XCD
-    const int nphys = NS < 8 ? (int)NS : 8 * m;
-    auto owner = [&](long long j) -> int {
-        if (NS < 8) return (int)j;
-        const long long x = j / per_x, jj = j % per_x;
-        return (int)(8 * (jj % m) + x);
-    };
-    std::vector<std::vector<KnnWork>> blk(nphys);
-    long long pos = 0;
-    struct Piece { int b, t0, t1, k, owner; };
-    std::vector<Piece> pieces;
-    std::vector<int> cnt, last_owner;
+    const KnnSchedule S = knn_schedule(in, c->knn_grid, c->n_cu, max_iters, knn_knobs());
+    c->h_probs.assign(n, ProbDev{});
     for (int i = 0; i < n; ++i) {
         ProbDev& P = c->h_probs[i];
+        const KnnSchedSlot& s = S.slots[i];
         P.q = c->sets[problems[i].query_set].d;
         P.t = c->sets[problems[i].train_set].d;
-        if (bin[i]) {
-            // Train rows are cut into splits only while the query blocks alone would leave CUs idle (one
-            // 64 x 70,000 problem must not run on one block): about four work items per CU over the
-            // batch's binary problems, a split no shorter than four tiles.
-            const int hq = (P.q.n + kHamBlockQ - 1) / kHamBlockQ;
-            const int tiles = (P.t.n + kHamTileRows - 1) / kHamTileRows;
-            const long long want = (4LL * c->n_cu + ham_qb - 1) / std::max<long long>(ham_qb, 1);
-            P.nsplit = (int)std::max<long long>(1, std::min<long long>(want, tiles / 4));
-            P.q_pad = std::max(hq, 1) * kHamBlockQ;
-            P.part_off = part;
-            part += (long long)P.nsplit * P.q_pad;
-            P.good_off = good;
-            good += (std::max(P.q.n, 1) + 31) & ~31;
-            P.it_off = it;
-            it += std::max(max_iters, 1);
-            continue;
-        }
-        const int qb = (P.q.n + kKnnBlockQ - 1) / kKnnBlockQ, nt = P.t.n_tiles;
-        const int nseg = (sub_target >= 0 && nt > sub) ? (int)((nt + sub - 1) / sub) : 1;
-        const int lseg = nseg > 1 ? (nt + nseg - 1) / nseg : nt;
-        pieces.clear();
-        cnt.assign(qb, 0);
-        last_owner.assign(qb, owner(std::min(NS - 1, pos / sub)));
-        for (int sg = 0; sg < nseg; ++sg) {
-            const int s0 = sg * lseg, s1 = std::min(nt, s0 + lseg);
-            for (int b = 0; b < qb && s0 < s1; ++b) {
-                const long long u0 = pos, u1 = pos + (s1 - s0);
-                for (long long a = u0; a < u1;) {
-                    const long long e = std::min(u1, (a / sub + 1) * sub);
-                    const int o = owner(std::min(NS - 1, a / sub));
-                    pieces.push_back(Piece{b, s0 + (int)(a - u0), s0 + (int)(e - u0), cnt[b]++, o});
-                    last_owner[b] = o;
-                    a = e;
-                }
-                pos = u1;
-            }
-        }
-        int nsplit = 1;
-        for (int b = 0; b < qb; ++b) nsplit = std::max(nsplit, cnt[b]);
-        P.nsplit = nsplit;
-        P.q_pad = qb * kKnnBlockQ;
-        P.part_off = part;
-        part += (long long)nsplit * P.q_pad;
-        P.good_off = good;
-        good += (std::max(P.q.n, 1) + 31) & ~31;  // 32-aligned: the MFMA bound's point tiles
-        P.it_off = it;
-        it += std::max(max_iters, 1);
-        for (const Piece& pc : pieces) blk[pc.owner].push_back(KnnWork{i, pc.b * kKnnBlockQ, pc.t0, pc.t1, pc.k});
-        for (int b = 0; b < qb; ++b)
-            for (int k = cnt[b]; k < nsplit; ++k)
-                blk[last_owner[b]].push_back(KnnWork{i, b * kKnnBlockQ, nt, nt, k});  // empty split
+        P.nsplit = s.nsplit;
+        P.q_pad = s.q_pad;
+        P.part_off = s.part_off;
+        P.good_off = s.good_off;
+        P.it_off = s.it_off;
     }
-    std::vector<KnnWork> works;
-    std::vector<int> seg;
-    int n_launch = nphys;
-    if (dyn) {
-        // MIM_KNN_DYN=1: whole query-block sweeps (one split per problem), in unit order, as 8 contiguous
-        // lists of about equal work (one per XCD); the resident blocks pull them (knn2_i8_kernel).
-        // The tail: when the sweeps do not fill the last round of the G resident blocks (a per-GPU shard
-        // of 32 C4 problems is 640 sweeps over 512 blocks: two rounds, the second a quarter full), the
-        // trailing problems covering that remainder are cut into k train-tile pieces per query block
-        // (k ~ G / their sweeps, <= 8), which every list holds after its whole sweeps: the blocks
-        // that finish early pull pieces and the kernel ends near sweeps / G rounds instead of the
-        // ceiling (each piece repeats the keyed early tiles and the prologue, a few per cent of a
-        // sweep; partial top-2 lists merged by the ratio kernel).  Opt-in (MIM_KNN_TAIL=1): it shortens a
-        // batch alone (32-problem shard: 0.48 -> 0.45 ms) but costs throughput once batches overlap (the
-        // pieces' extra early tiles and merge work: 32-problem shard with 12 in flight 26.8k -> 25.5k
-        // problems/s, profiles/r05i_*), and the bench keeps batches in flight.
-        works.clear();
-        const char* tail_env = getenv("MIM_KNN_TAIL");
-        const long long rem = n_sweeps % G;
-        int tail_from = n, ksplit = 1;
-        if (tail_env && atoi(tail_env) != 0 && n_sweeps > G && rem > 0) {
-            long long ts = 0;
-            while (tail_from > 0 && ts < rem) {
-                --tail_from;
-                if (!bin[tail_from]) ts += c->h_probs[tail_from].q_pad / kKnnBlockQ;
-            }
-            ksplit = (int)std::max<long long>(2, std::min<long long>(8, (G + ts / 2) / ts));
-        }
-        long long total = 0, total_t = 0;
-        for (int i = 0; i < n; ++i) {
-            if (bin[i]) continue;
-            ProbDev& P = c->h_probs[i];
-            const int qb = P.q_pad / kKnnBlockQ;
-            P.nsplit = 1;
-            if (i >= tail_from) continue;
-            for (int b = 0; b < qb; ++b) works.push_back(KnnWork{i, b * kKnnBlockQ, 0, P.t.n_tiles, 0});
-            total += (long long)qb * P.t.n_tiles;
-        }
-        std::vector<KnnWork> tail;
-        for (int i = tail_from; i < n; ++i) {  // pieces in (problem, tile range, query block) order
-            if (bin[i]) continue;
-            ProbDev& P = c->h_probs[i];
-            const int qb = P.q_pad / kKnnBlockQ, nt = P.t.n_tiles, k = std::min(ksplit, std::max(nt, 1));
-            P.nsplit = k;
-            for (int j = 0; j < k; ++j)
-                for (int b = 0; b < qb; ++b) tail.push_back(KnnWork{i, b * kKnnBlockQ, j * nt / k, (j + 1) * nt / k, j});
-            total_t += (long long)qb * nt;
-        }
-        part = 0;
-        for (int i = 0; i < n; ++i) {
-            c->h_probs[i].part_off = part;
-            part += (long long)c->h_probs[i].nsplit * c->h_probs[i].q_pad;
-        }
-        // 8 lists, each [its eighth of the whole sweeps | its eighth of the pieces], equal work per part
-        auto cuts = [&](const std::vector<KnnWork>& v, long long tot) {
-            std::vector<int> cut(9, (int)v.size());
-            cut[0] = 0;
-            long long acc = 0;
-            int x = 1;
-            for (size_t k = 0; k < v.size() && x < 8; ++k) {
-                acc += v[k].tile1 - v[k].tile0;
-                while (x < 8 && acc * 8 >= tot * x) cut[x++] = (int)k + 1;
-            }
-            return cut;
-        };
-        const std::vector<int> cw = cuts(works, total), ct = cuts(tail, total_t);
-        std::vector<KnnWork> all;
-        all.reserve(works.size() + tail.size());
-        seg.assign(9, 0);
-        for (int x = 0; x < 8; ++x) {
-            seg[x] = (int)all.size();
-            all.insert(all.end(), works.begin() + cw[x], works.begin() + cw[x + 1]);
-            all.insert(all.end(), tail.begin() + ct[x], tail.begin() + ct[x + 1]);
-        }
-        seg[8] = (int)all.size();
-        works.swap(all);
-        n_launch = (int)std::min<long long>(G, std::max<size_t>(works.size(), 8));
-        n_launch = std::max(8, n_launch / 8 * 8);
-    } else {
-        seg.assign(nphys + 1, 0);
-        for (int b = 0; b < nphys; ++b) {
-            seg[b] = (int)works.size();
-            works.insert(works.end(), blk[b].begin(), blk[b].end());
-        }
-        seg[nphys] = (int)works.size();
-    }
+    const std::vector<KnnWork>& works = S.works;
+    const std::vector<int>& seg = S.seg;
+    const long long part = S.part, good = S.good;
     HIPCHK(c, c->probs.ensure(sizeof(ProbDev) * std::max(n, 1)));
     HIPCHK(c, c->works.ensure(sizeof(KnnWork) * std::max<size_t>(works.size(), 1) + sizeof(int) * seg.size()));
     HIPCHK(c, c->parts.ensure(sizeof(Top2) * std::max<long long>(part, 1)));
-    // Hamming work list of the binary problems: (problem, query block, train row range of one split)
+    // the Hamming pieces with their pointers (parts is sized above)
     std::vector<HamWork> ham;
-    for (int i = 0; i < n; ++i) {
-        if (!bin[i]) continue;
-        const ProbDev& P = c->h_probs[i];
-        const int hq = (P.q.n + kHamBlockQ - 1) / kHamBlockQ;
-        const int tiles = (P.t.n + kHamTileRows - 1) / kHamTileRows;
-        const int wdw = c->sets[problems[i].query_set].bin_pad / 4;
-        for (int sp = 0; sp < P.nsplit; ++sp) {
-            const int r0 = (int)((long long)sp * tiles / P.nsplit) * kHamTileRows;
-            const int r1 = std::min(P.t.n, (int)((long long)(sp + 1) * tiles / P.nsplit) * kHamTileRows);
-            for (int b = 0; b < hq; ++b)
-                ham.push_back(HamWork{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
-                                      c->parts.as<Top2>() + P.part_off + (long long)sp * P.q_pad, P.q.n,
-                                      b * kHamBlockQ, r0, std::max(r0, r1), wdw, 0});
-        }
+    ham.reserve(S.ham.size());
+    for (const HamPiece& hp : S.ham) {
+        const ProbDev& P = c->h_probs[hp.problem];
+        const int wdw = c->sets[problems[hp.problem].query_set].bin_pad / 4;
+        ham.push_back(HamWork{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
+                              c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, P.q.n, hp.q0, hp.r0,
+                              hp.r1, wdw, 0});
     }
     if (!ham.empty()) HIPCHK(c, c->ham_works.ensure(sizeof(HamWork) * ham.size()));
     HIPCHK(c, c->good_q.ensure(sizeof(int32_t) * good));
@@ -861,9 +685,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     for (int i = 0; i < n; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
     c->last_n = n;
     c->n_works = (int)works.size();
-    c->n_knn_blocks = n_launch;
-    c->knn_dyn = dyn;
-    if (dyn) HIPCHK(c, c->knn_ctr.ensure(8 * sizeof(int)));
+    c->n_knn_blocks = S.n_blocks;
+    c->knn_dyn = S.dyn;
+    if (S.dyn) HIPCHK(c, c->knn_ctr.ensure(8 * sizeof(int)));
     return MIM_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_schedule.h"  // KnnWork, kKnnBlockQ and what it is derived from, the Hamming block constants
+
 namespace mim {
 
 constexpr int kDim = 128;          // SIFT descriptor length (TestsDetector.cpp:60 operands)
@@ -11,25 +13,10 @@ constexpr int kTileRows = 64;      // descriptor rows per staged tile
 constexpr int kTileBytes = kTileRows * kDim;  // 8 KiB of i8 per tile
 constexpr int kNormWords = 4 * kTileRows;      // norm block per tile (knn.hip prep_tile)
 constexpr int kWave = 64;
-#ifndef MIM_KNN_QT
-#define MIM_KNN_QT 2
-#endif
-
-#ifndef MIM_KNN_WAVES
-#define MIM_KNN_WAVES 8
-#endif
 #ifndef MIM_KNN_STAGE
 #define MIM_KNN_STAGE 4
 #endif
-constexpr int kKnnQT = MIM_KNN_QT;             // 32-query MFMA column tiles per wave (distance kernel)
-constexpr int kKnnWaves = MIM_KNN_WAVES;       // waves per distance-kernel block
 constexpr int kKnnStage = MIM_KNN_STAGE;       // 64-row train tiles per LDS stage (per barrier)
-constexpr int kKnnMinChunk = 8;                // fewest train tiles per distance-kernel block
-#ifndef MIM_KNN_SUB_TILES
-#define MIM_KNN_SUB_TILES -1
-#endif
-constexpr int kKnnSubTiles = MIM_KNN_SUB_TILES;  // distance schedule's sub-chunk target (api.cpp build_tables)
-constexpr int kKnnBlockQ = kKnnWaves * 32 * kKnnQT;  // queries per distance-kernel work item
 
 // One descriptor set = one ObjectModel view (objectModel.hpp:11-16) or one scaled scene
 // (TestsDetector.cpp:104-106), resident in HBM.
@@ -67,23 +54,10 @@ struct ProbDev {
     long long it_off;    // into per-iteration arrays (capacity max_iters)
 };
 
-// Segment of the distance kernel: kKnnBlockQ queries x a train tile range of one problem, written
-// to train split `split`.  A block runs the segments seg_start[b] .. seg_start[b + 1] - 1 (api.cpp
-// build_tables: one balanced chunk of the batch's tiles per resident block).
-struct KnnWork {
-    int problem;
-    int q0;        // first query row (multiple of kKnnBlockQ)
-    int tile0;     // train tiles [tile0, tile1)
-    int tile1;
-    int split;
-};
-
 // Binary descriptor sets (hamming.hip, DESIGN.md "Binary descriptors").  Such a set's SetDev has
 // frag = its rows zero-padded to 16, 32 or 64 bytes (zero rows up to the next multiple of kHamTileRows
 // past the last row), kp and n; norm, f32 and flags are null.  The padded width is host knowledge
-// (api.cpp SetRec), carried to the device in each work item.
-constexpr int kHamBlockQ = 256;    // queries per Hamming work item
-constexpr int kHamTileRows = 128;  // train rows per LDS stage
+// (api.cpp SetRec), carried to the device in each work item.  kHamBlockQ, kHamTileRows: knn_schedule.h.
 
 // Work item of the Hamming kernel: kHamBlockQ queries from q0 x train rows [r0, r1) of one problem,
 // written to one train split.  r0 is a multiple of kHamTileRows.

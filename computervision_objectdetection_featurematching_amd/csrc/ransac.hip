@@ -2627,7 +2627,7 @@ __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restri
     RansacState* Sp = st + p;
     if (!Sp->active || Sp->done) return;
     const int n = Sp->n;
-    const long long go = probs[p].good_off;  // multiple of 32 (build_tables)
+    const long long go = probs[p].good_off;  // multiple of 32 (knn_layout_offsets)
     const float4* __restrict__ P = pts + go;
     float mxy = 0.f, muv = 0.f, ms = 0.f;
     for (int i = tid; i < n; i += 256) {
