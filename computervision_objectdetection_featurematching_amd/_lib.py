@@ -26,6 +26,7 @@ EXPORTS = [
     "mim_group_results",
     "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_group_scene_images_run", "mim_group_scene_points",
     "mim_set_create_bin", "mim_knn2_hamming",
+    "mim_set_create_f32", "mim_knn2_l2_f32",
 ]
 
 
@@ -101,6 +102,8 @@ def load():
     L.mim_set_create.argtypes = [vp, f32p, f32p, i32, i32, i32, C.POINTER(C.c_int32)]
     L.mim_set_create_bin.argtypes = [vp, u8p, C.c_int64, f32p, i32, i32, i32, C.POINTER(C.c_int32)]
     L.mim_knn2_hamming.argtypes = [vp, u8p, i32, u8p, i32, i32, i32p, f32p]
+    L.mim_set_create_f32.argtypes = [vp, f32p, C.c_int64, f32p, i32, i32, i32, C.POINTER(C.c_int32)]
+    L.mim_knn2_l2_f32.argtypes = [vp, f32p, i32, f32p, i32, i32, i32p, f32p]
     L.mim_sets_create.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), i32p, i32, i32, C.POINTER(C.c_int32)]
     L.mim_sets_clear.argtypes = [vp]
     L.mim_sets_truncate.argtypes = [vp, i32]
@@ -149,7 +152,7 @@ def load():
     for name in ("mim_group_shard", "mim_group_create", "mim_group_size", "mim_group_uses_rccl", "mim_group_set_create",
                  "mim_group_scene_batch_run", "mim_group_results", "mim_group_scene_images_run",
                  "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_set_create_bin",
-                 "mim_knn2_hamming"):
+                 "mim_knn2_hamming", "mim_set_create_f32", "mim_knn2_l2_f32"):
         getattr(L, name).restype = C.c_int32
     for name in ("mim_ctx_create", "mim_ctx_set_stream", "mim_synchronize", "mim_set_create", "mim_sets_create", "mim_sets_clear",
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",

@@ -29,6 +29,7 @@ void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const i
                 int* dyn_ctr, float kappa, hipStream_t st);
 int knn_blocks_per_cu();
 void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
+void launch_knn_float(const FltWork* works, int n_works, hipStream_t st);
 void launch_ratio(const ProbDev* probs, int n_probs, const Top2* parts, float ratio, int32_t* good_q,
                   int32_t* good_t, float4* pts, int* n_good, int32_t* knn_idx, float* knn_dist,
                   hipStream_t st);
@@ -110,6 +111,8 @@ struct SetRec {
     Arena::Mark mark;  // the arena before the set's storage (mim_sets_truncate)
     int bin_pad = 0;   // binary set: bytes per padded row (16, 32 or 64); 0: a float set
     int bin_width = 0; // binary set: the caller's bytes per row
+    int fdim = 0;      // generic float set (mim_set_create_f32): floats per row, 1..kFltMaxDim; 0: not one
+    int fpad = 0;      // generic float set: floats per stored row (fdim rounded up to a multiple of 4)
 };
 
 // Pinned staging for the per-batch tables, two generations: a batch's host->device table copies
@@ -176,10 +179,11 @@ struct mim_ctx {
     Arena arena;
     std::vector<SetRec> sets;
     // batch workspace
-    DevBuf probs, works, parts, good_q, good_t, pts, n_good, results, masks, knn_idx, knn_dist, inl_tab, inl_out, knn_ctr, ham_works;
+    DevBuf probs, works, parts, good_q, good_t, pts, n_good, results, masks, knn_idx, knn_dist, inl_tab, inl_out, knn_ctr, ham_works, flt_works;
     RansacWs rws;
     std::vector<ProbDev> h_probs;
     int n_ham_works = 0;  // Hamming work items of the current batch (its binary problems)
+    int n_flt_works = 0;  // generic-float work items of the current batch
     int n_cu = 0;         // compute units of the device (first batch)
     int n_works = 0;  // distance segments of the current batch (works, then the per-block segment starts)
     std::vector<long long> h_good_off;
@@ -309,7 +313,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -477,6 +481,60 @@ mim_status mim_set_create_bin(mim_ctx* c, const uint8_t* desc, int64_t step, con
     return set_create_bin_locked(c, desc, step, kp, n, width, on_device, set_id);
 }
 
+// A generic float set: rows copied into the library's own storage (never borrowed) at a stride of dim
+// rounded up to 4 floats, zero filled, with zero rows up to the next multiple of kFltRowPad (the float
+// kernel stages whole tiles and never inserts a row past n).  No prep job and no flags: the host knows
+// the kind, so such a set never takes the i8 path.
+static mim_status set_create_f32_locked(mim_ctx* c, const float* desc, int64_t step, const float* kp, int32_t n,
+                                        int32_t dim, int32_t on_device, int32_t* set_id) {
+    if (!set_id || n < 0 || (n > 0 && (!desc || !kp))) return fail(c, MIM_EINVAL, "set_create_f32: bad arguments");
+    if (dim < 1 || dim > kFltMaxDim)
+        return fail(c, MIM_EINVAL, "set_create_f32: dim must be 1..%d (got %d)", kFltMaxDim, dim);
+    if (step < (int64_t)4 * dim || step % 4 != 0)
+        return fail(c, MIM_EINVAL, "set_create_f32: step %lld must be a multiple of 4 and >= 4 * dim = %d",
+                    (long long)step, 4 * dim);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int dp = (dim + 3) & ~3;
+    const size_t rows = (size_t)std::max((n + kFltRowPad - 1) / kFltRowPad, 1) * kFltRowPad;
+    const size_t bytes = rows * dp * sizeof(float);
+    SetRec r{};
+    r.mark = c->arena.pos();
+    r.fdim = dim;
+    r.fpad = dp;
+    r.d.n = n;
+    r.d.n_tiles = (n + 63) / 64;
+    void *dd = nullptr, *dk = nullptr;
+    auto undo = [&](mim_status st) {
+        c->arena.seek(r.mark);
+        return st;
+    };
+    if (c->arena.alloc(bytes, &dd) != hipSuccess || c->arena.alloc((size_t)std::max(n, 1) * sizeof(float2), &dk) != hipSuccess)
+        return undo(fail(c, MIM_ENOMEM, "set_create_f32: device allocation of %zu bytes failed", bytes));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipError_t e = hipMemsetAsync(dd, 0, bytes, c->stream);
+    if (e == hipSuccess && n > 0)
+        e = hipMemcpy2DAsync(dd, (size_t)dp * sizeof(float), desc, (size_t)step, (size_t)dim * sizeof(float), (size_t)n,
+                             kind, c->stream);
+    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dk, kp, (size_t)n * sizeof(float2), kind, c->stream);
+    if (e == hipSuccess && !on_device) e = hipStreamSynchronize(c->stream);  // host buffers may go away
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        return undo(fail(c, MIM_EDEVICE, "set_create_f32: copy failed: %s", hipGetErrorString(e)));
+    }
+    r.d.f32 = (const float*)dd;
+    r.d.kp = (const float2*)dk;
+    *set_id = (int32_t)c->sets.size();
+    c->sets.push_back(r);
+    return MIM_OK;
+}
+
+mim_status mim_set_create_f32(mim_ctx* c, const float* desc, int64_t step, const float* kp, int32_t n, int32_t dim,
+                              int32_t on_device, int32_t* set_id) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return set_create_f32_locked(c, desc, step, kp, n, dim, on_device, set_id);
+}
+
 static void sets_truncate_locked(mim_ctx* c, int n_keep);
 
 mim_status mim_sets_create(mim_ctx* c, int32_t count, const float* const* desc, const float* const* kp,
@@ -576,6 +634,9 @@ mim_status mim_set_rows(mim_ctx* c, int32_t set_id, int32_t cap, float* desc, fl
         return fail(c, MIM_EINVAL, "set_rows: set %d not registered (%d sets)", set_id, (int)c->sets.size());
     if (c->sets[set_id].bin_pad)
         return fail(c, MIM_EINVAL, "set_rows: set %d holds binary descriptors, not float rows", set_id);
+    if (c->sets[set_id].fdim)
+        return fail(c, MIM_EINVAL, "set_rows: set %d holds generic float rows of dim %d, not 128-column rows", set_id,
+                    c->sets[set_id].fdim);
     HIPCHK(c, hipSetDevice(c->device));
     const SetDev& d = c->sets[set_id].d;
     *n_rows = d.n;
@@ -628,7 +689,14 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         if (Q.bin_width != T.bin_width)
             return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
                         T.bin_width);
+        if ((Q.fdim != 0) != (T.fdim != 0))
+            return fail(c, MIM_EINVAL, "problem %d: set %d holds %s rows and set %d %s ones", i, qs,
+                        Q.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)", ts,
+                        T.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
+        if (Q.fdim != T.fdim)
+            return fail(c, MIM_EINVAL, "problem %d: generic float sets of different dims (%d and %d)", i, Q.fdim, T.fdim);
         in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
+        in[i].fdim = Q.fdim;
     }
     const KnnSchedule S = knn_schedule(in, c->knn_grid, c->n_cu, max_iters, knn_knobs());
     c->h_probs.assign(n, ProbDev{});
@@ -660,6 +728,16 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
                               hp.r1, wdw, 0});
     }
     if (!ham.empty()) HIPCHK(c, c->ham_works.ensure(sizeof(HamWork) * ham.size()));
+    // and the generic-float pieces
+    std::vector<FltWork> flt;
+    flt.reserve(S.flt.size());
+    for (const FltPiece& fp : S.flt) {
+        const ProbDev& P = c->h_probs[fp.problem];
+        const SetRec& Q = c->sets[problems[fp.problem].query_set];
+        flt.push_back(FltWork{P.q.f32, P.t.f32, c->parts.as<Top2>() + P.part_off + (long long)fp.split * P.q_pad, P.q.n,
+                              fp.q0, fp.r0, fp.r1, Q.fdim, Q.fpad});
+    }
+    if (!flt.empty()) HIPCHK(c, c->flt_works.ensure(sizeof(FltWork) * flt.size()));
     HIPCHK(c, c->good_q.ensure(sizeof(int32_t) * good));
     HIPCHK(c, c->good_t.ensure(sizeof(int32_t) * good));
     HIPCHK(c, c->pts.ensure(sizeof(float4) * good));
@@ -667,9 +745,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     HIPCHK(c, c->masks.ensure(good));
     // the device tables are rewritten in stream order (after the previous batch's kernels)
     const size_t pb = sizeof(ProbDev) * n, wb = sizeof(KnnWork) * works.size(), sb = sizeof(int) * seg.size();
-    const size_t hb = sizeof(HamWork) * ham.size();
+    const size_t hb = sizeof(HamWork) * ham.size(), fb = sizeof(FltWork) * flt.size();
     char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb, &st));
+    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb + fb, &st));
     memcpy(st, c->h_probs.data(), pb);
     memcpy(st + pb, works.data(), wb);
     memcpy(st + pb + wb, seg.data(), sb);
@@ -679,7 +757,12 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         memcpy(st + pb + wb + sb, ham.data(), hb);
         HIPCHK(c, hipMemcpyAsync(c->ham_works.p, st + pb + wb + sb, hb, hipMemcpyHostToDevice, c->stream));
     }
+    if (fb) {
+        memcpy(st + pb + wb + sb + hb, flt.data(), fb);
+        HIPCHK(c, hipMemcpyAsync(c->flt_works.p, st + pb + wb + sb + hb, fb, hipMemcpyHostToDevice, c->stream));
+    }
     c->n_ham_works = (int)ham.size();
+    c->n_flt_works = (int)flt.size();
     HIPCHK(c, c->stage.release_after(c->stream));
     c->h_good_off.resize(n);
     for (int i = 0; i < n; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
@@ -744,6 +827,7 @@ static void knn_launch(mim_ctx* c, float kappa = 0.f) {
     launch_knn(c->probs.as<ProbDev>(), w, c->n_works, reinterpret_cast<const int*>(w + c->n_works), c->n_knn_blocks,
                c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, kappa, c->cur);
     launch_knn_hamming(c->ham_works.as<HamWork>(), c->n_ham_works, c->cur);
+    launch_knn_float(c->flt_works.as<FltWork>(), c->n_flt_works, c->cur);
 }
 
 // distance + ratio kernels of the batch's problems
@@ -836,6 +920,49 @@ mim_status mim_knn2_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint
     const mim_status s = run();
     ev_collect(c);
     // the private sets own their storage and nothing was registered after them: both go
+    c->sets.resize(base);
+    if (reclaim) c->arena.seek(mark);
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    return s;
+}
+
+mim_status mim_knn2_l2_f32(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
+                           int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
+        return fail(c, MIM_EINVAL, "knn2_l2_f32: bad arguments");
+    if (dim < 1 || dim > kFltMaxDim)
+        return fail(c, MIM_EINVAL, "knn2_l2_f32: dim must be 1..%d (got %d)", kFltMaxDim, dim);
+    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    // private sets appended after the user's sets, removed afterwards (as mim_knn2_hamming)
+    const size_t base = c->sets.size();
+    const Arena::Mark mark = c->arena.pos();
+    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
+    const bool reclaim = c->pend.empty();  // see mim_knn2_hamming
+    auto run = [&]() -> mim_status {
+        int32_t sq, st;
+        mim_status s = set_create_f32_locked(c, q, (int64_t)4 * dim, kp0.data(), nq, dim, 0, &sq);
+        if (s != MIM_OK) return s;
+        s = set_create_f32_locked(c, t, (int64_t)4 * dim, kp0.data(), nt, dim, 0, &st);
+        if (s != MIM_OK) return s;
+        mim_problem pr{sq, st};
+        s = build_tables(c, &pr, 1, 1);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * 2 * nq));
+        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * 2 * nq));
+        s = knn_ratio_locked(c, 1, 0.9f, true);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return MIM_OK;
+    };
+    const mim_status s = run();
+    ev_collect(c);
     c->sets.resize(base);
     if (reclaim) c->arena.seek(mark);
     c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)

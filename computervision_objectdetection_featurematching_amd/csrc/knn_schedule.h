@@ -37,13 +37,21 @@ struct KnnWork {
 constexpr int kHamBlockQ = 256;    // queries per Hamming work item
 constexpr int kHamTileRows = 128;  // train rows per LDS stage
 
+constexpr int kFltBlockQ = 256;  // queries per generic-float work item (one per lane, 4 waves)
+constexpr int kFltRowPad = 64;   // a generic-float set's stored rows are a multiple of this; split unit
+constexpr int kFltMaxDim = 512;  // widest generic-float row
+
 // What the schedule knows of one problem.
 struct KnnSchedProblem {
     int nq;       // query rows
     int nt;       // train rows
     int n_tiles;  // train tiles (SetDev::n_tiles)
     bool bin;     // binary descriptors: the Hamming work list, not the i8 schedule
+    int fdim = 0; // generic float rows of this dim (mim_set_create_f32): the float work list, not the i8 schedule
 };
+
+// problems of the i8 schedule: neither binary nor generic-float
+inline bool knn_is_i8(const KnnSchedProblem& p) { return !p.bin && p.fdim == 0; }
 
 // MIM_KNN_SUB, MIM_KNN_DYN and MIM_KNN_TAIL, read by the caller.
 struct KnnSchedKnobs {
@@ -65,6 +73,12 @@ struct HamPiece {
     int problem, q0, r0, r1, split;
 };
 
+// Work item of the generic-float kernel without its pointers: kFltBlockQ queries from q0 x train rows
+// [r0, r1) of one problem (r0 a multiple of kFltRowPad), written to train split `split`.
+struct FltPiece {
+    int problem, q0, r0, r1, split;
+};
+
 struct KnnSchedule {
     std::vector<KnnSchedSlot> slots;  // per problem
     std::vector<KnnWork> works;
@@ -73,6 +87,7 @@ struct KnnSchedule {
     bool dyn = false;
     long long part = 0, good = 0;  // Top2 partials and good-match slots over the batch
     std::vector<HamPiece> ham;
+    std::vector<FltPiece> flt;
 };
 
 inline int knn_query_blocks(int nq) { return (nq + kKnnBlockQ - 1) / kKnnBlockQ; }
@@ -93,7 +108,7 @@ inline void knn_schedule_static(const std::vector<KnnSchedProblem>& in, long lon
     const int n = (int)in.size();
     long long units = 0;
     for (int i = 0; i < n; ++i)
-        if (!in[i].bin) units += (long long)knn_query_blocks(in[i].nq) * in[i].n_tiles;
+        if (knn_is_i8(in[i])) units += (long long)knn_query_blocks(in[i].nq) * in[i].n_tiles;
     const long long chunk = std::max<long long>(kKnnMinChunk, (units + G - 1) / G);
     const long long R = (sub_target > 0 && chunk > sub_target) ? (chunk + sub_target - 1) / sub_target : 1;
     const long long sub = std::max<long long>(kKnnMinChunk, (chunk + R - 1) / R);
@@ -112,7 +127,7 @@ inline void knn_schedule_static(const std::vector<KnnSchedProblem>& in, long lon
     std::vector<Piece> pieces;
     std::vector<int> cnt, last_owner;
     for (int i = 0; i < n; ++i) {
-        if (in[i].bin) continue;
+        if (!knn_is_i8(in[i])) continue;
         const int qb = knn_query_blocks(in[i].nq), nt = in[i].n_tiles;
         const int nseg = (sub_target >= 0 && nt > sub) ? (int)((nt + sub - 1) / sub) : 1;
         const int lseg = nseg > 1 ? (nt + nseg - 1) / nseg : nt;
@@ -172,14 +187,14 @@ inline void knn_schedule_dynamic(const std::vector<KnnSchedProblem>& in, long lo
         long long ts = 0;
         while (tail_from > 0 && ts < rem) {
             --tail_from;
-            if (!in[tail_from].bin) ts += knn_query_blocks(in[tail_from].nq);
+            if (knn_is_i8(in[tail_from])) ts += knn_query_blocks(in[tail_from].nq);
         }
         ksplit = (int)std::max<long long>(2, std::min<long long>(8, (G + ts / 2) / ts));
     }
     std::vector<KnnWork> works, tail;
     long long total = 0, total_t = 0;
     for (int i = 0; i < n; ++i) {  // pieces in (problem, tile range, query block) order
-        if (in[i].bin) continue;
+        if (!knn_is_i8(in[i])) continue;
         const int qb = knn_query_blocks(in[i].nq), nt = in[i].n_tiles;
         const int k = i < tail_from ? 1 : std::min(ksplit, std::max(nt, 1));
         S.slots[i].nsplit = k;
@@ -243,6 +258,58 @@ inline void knn_hamming_plan(const std::vector<KnnSchedProblem>& in, int n_cu, K
     }
 }
 
+// Work list of the generic-float problems (knn_float.hip): (problem, query block, train row range of one
+// split).  Train rows are cut into splits of whole kFltRowPad-row units only while the query blocks alone
+// would leave CUs idle (fewer than four per CU over the batch's generic-float problems), a split no
+// shorter than four units.  The kernel is VALU-bound, so a CU finishes its blocks one after another
+// however many are resident: the common split count w is the one with the least
+// ceil(items / CUs) x (rows of the longest item + kFltItemRows), the time of the CU with the most items
+// (one 10,000 x 10,000 problem, 40 query blocks on 256 CUs: w = 32, 1,280 items in 5 even rounds, where
+// 26 splits would leave a sixth round of 16 items).
+constexpr int kFltItemRows = 24;  // an item's fixed cost in train rows (query load, first tile's insertions, launch)
+inline void knn_float_plan(const std::vector<KnnSchedProblem>& in, int n_cu, KnnSchedule& S) {
+    const int n = (int)in.size();
+    long long flt_qb = 0;  // their query blocks
+    int max_units = 0;
+    for (int i = 0; i < n; ++i)
+        if (in[i].fdim) {
+            flt_qb += (in[i].nq + kFltBlockQ - 1) / kFltBlockQ;
+            if (in[i].nq > 0) max_units = std::max(max_units, (in[i].nt + kFltRowPad - 1) / kFltRowPad);
+        }
+    int w_best = 1;
+    if (flt_qb < 4LL * n_cu && max_units >= 8) {
+        const int w_max = (int)std::min<long long>(max_units / 4, 4LL * n_cu);
+        long long best = -1;
+        for (int w = 1; w <= w_max; ++w) {
+            long long items = 0;
+            for (int i = 0; i < n; ++i)
+                if (in[i].fdim) {
+                    const int units = (in[i].nt + kFltRowPad - 1) / kFltRowPad;
+                    items += (long long)((in[i].nq + kFltBlockQ - 1) / kFltBlockQ) * std::max(1, std::min(w, units / 4));
+                }
+            const long long rows = (long long)((max_units + w - 1) / w) * kFltRowPad + kFltItemRows;
+            const long long cost = (items + n_cu - 1) / n_cu * rows;
+            if (best < 0 || cost < best) {
+                best = cost;
+                w_best = w;
+            }
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!in[i].fdim) continue;
+        KnnSchedSlot& P = S.slots[i];
+        const int fq = (in[i].nq + kFltBlockQ - 1) / kFltBlockQ;
+        const int units = (in[i].nt + kFltRowPad - 1) / kFltRowPad;
+        P.nsplit = std::max(1, std::min(w_best, units / 4));
+        P.q_pad = std::max(fq, 1) * kFltBlockQ;
+        for (int sp = 0; sp < P.nsplit; ++sp) {
+            const int r0 = (int)((long long)sp * units / P.nsplit) * kFltRowPad;
+            const int r1 = std::min(in[i].nt, (int)((long long)(sp + 1) * units / P.nsplit) * kFltRowPad);
+            for (int b = 0; b < fq; ++b) S.flt.push_back(FltPiece{i, b * kFltBlockQ, r0, std::max(r0, r1), sp});
+        }
+    }
+}
+
 // The problems' shares of the partials ([split][q_pad] each), the good-match arrays and the
 // per-iteration arrays, in problem order; after the split counts are known.
 inline void knn_layout_offsets(const std::vector<KnnSchedProblem>& in, int max_iters, KnnSchedule& S) {
@@ -266,7 +333,8 @@ inline KnnSchedule knn_schedule(const std::vector<KnnSchedProblem>& in, int G, i
     KnnSchedule S;
     S.slots.assign(in.size(), KnnSchedSlot{});
     // binary problems (both sets binary, one width) are known here, on the host: they stay out of the
-    // i8 schedule below and get the Hamming work list after it
+    // i8 schedule below and get the Hamming work list after it; so are generic-float problems (both
+    // sets registered with mim_set_create_f32, one dim), which get the float work list
 
     // Dynamic mode (whole sweeps pulled from per-XCD lists) when the batch has at least one query-block
     // sweep per resident block: fewer pieces (no early tiles and prologue per split) and a block that
@@ -276,13 +344,14 @@ inline KnnSchedule knn_schedule(const std::vector<KnnSchedProblem>& in, int G, i
     // MIM_KNN_DYN=0 / 1 forces either.
     long long n_sweeps = 0;
     for (const KnnSchedProblem& p : in)
-        if (!p.bin) n_sweeps += knn_query_blocks(p.nq);
+        if (knn_is_i8(p)) n_sweeps += knn_query_blocks(p.nq);
     S.dyn = knobs.dyn >= 0 ? knobs.dyn != 0 : n_sweeps >= G;
     if (S.dyn)
         knn_schedule_dynamic(in, G, n_sweeps, knobs.tail, S);
     else
         knn_schedule_static(in, G, knobs.sub_target, S);
     knn_hamming_plan(in, n_cu, S);
+    knn_float_plan(in, n_cu, S);
     knn_layout_offsets(in, max_iters, S);
     return S;
 }

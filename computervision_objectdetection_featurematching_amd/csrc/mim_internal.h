@@ -72,6 +72,24 @@ struct HamWork {
     int pad_;
 };
 
+// Generic float sets (knn_float.hip, DESIGN.md "Float descriptors of any dimension").  Such a set's
+// SetDev has f32 = its rows at a stride of `dp` floats (dim rounded up to a multiple of 4, zero filled;
+// zero rows up to the next multiple of kFltRowPad past the last row), kp and n; frag, norm and flags are
+// null.  dim is host knowledge (api.cpp SetRec), carried to the device in each work item.
+
+// Work item of the generic-float kernel: kFltBlockQ queries from q0 x train rows [r0, r1) of one
+// problem, written to one train split.  r0 is a multiple of kFltRowPad.
+struct FltWork {
+    const float* q;      // padded query rows of the problem
+    const float* t;      // padded train rows
+    Top2* out;           // the split's partials: parts + part_off + split * q_pad
+    int nq;
+    int q0;
+    int r0, r1;
+    int dim;             // floats per row as the caller gave them (1..kFltMaxDim)
+    int dp;              // floats per stored row: dim rounded up to a multiple of 4
+};
+
 // RANSAC state per problem (RANSACPointSetRegistrator::run locals, ptsetreg.cpp).
 struct RansacState {
     long long stream_pos;  // RNG draws consumed so far (all calls see RNG((uint64)-1))

@@ -177,6 +177,56 @@ class Matcher:
         self._n_sets = sid.value + 1
         return sid.value
 
+    def add_float_set(self, desc, kp) -> int:
+        """Register a set of float descriptors of any dimension 1..512 (mim_set_create_f32): the CV_32F rows
+        BFMatcher(NORM_L2) matches (SURF/KAZE 64, VGG, DAISY 200, SuperPoint 256, D2-Net 512, and 128-D rows
+        that are not integers: RootSIFT, HardNet), and their (n, 2) keypoints.
+
+        numpy arrays (float32 (n, dim), any row stride that is a multiple of 4 bytes; float32 keypoints), or
+        torch device tensors (float32 (n, dim) with unit column stride, contiguous float32 (n, 2)).  The rows
+        are copied, never borrowed: device tensors may be released once the matcher's stream has passed the
+        copy."""
+        on_dev = int(hasattr(desc, "is_cuda") and desc.is_cuda)
+        if not on_dev:
+            desc = np.asarray(desc)
+            if desc.dtype != np.float32 or desc.ndim != 2:
+                raise ValueError(f"add_float_set: descriptors must be a float32 (n, dim) array, got {desc.dtype} "
+                                 f"{desc.shape}")
+            if desc.shape[0] <= 1 or desc.strides[1] != 4 or desc.strides[0] < 4 * desc.shape[1] or desc.strides[0] % 4:
+                desc = np.ascontiguousarray(desc)  # anything but rows of unit-stride floats a fixed step apart
+            kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 2)
+            step = int(desc.strides[0]) if desc.shape[0] > 1 else 4 * int(desc.shape[1])
+        else:
+            import torch
+            if not (hasattr(kp, "is_cuda") and kp.is_cuda):
+                raise ValueError("add_float_set: keypoints must be on the device when the descriptors are")
+            if desc.dtype != torch.float32 or desc.dim() != 2 or (desc.numel() > 1 and desc.shape[1] > 1 and desc.stride(1) != 1):
+                raise ValueError(f"add_float_set: descriptors must be a float32 (n, dim) tensor with unit column "
+                                 f"stride, got {desc.dtype} {tuple(desc.shape)}")
+            if kp.dtype != torch.float32 or not kp.is_contiguous() or kp.dim() != 2 or kp.shape[1] != 2:
+                raise ValueError(f"add_float_set: keypoints must be a contiguous float32 (n, 2) tensor, got "
+                                 f"{kp.dtype} {tuple(kp.shape)}")
+            for name, t in (("descriptors", desc), ("keypoints", kp)):
+                if t.device.index != self.device:
+                    raise ValueError(f"add_float_set: {name} on {t.device}, matcher on cuda:{self.device}")
+            step = 4 * (int(desc.stride(0)) if desc.shape[0] > 1 else int(desc.shape[1]))
+            mine = torch.cuda.ExternalStream(self.stream_handle(), device=desc.device)
+            cur = torch.cuda.current_stream(desc.device)
+            if cur.cuda_stream != mine.cuda_stream:
+                mine.wait_stream(cur)
+        if int(kp.shape[0]) != int(desc.shape[0]):
+            raise ValueError("add_float_set: descriptor and keypoint row counts differ")
+        sid = C.c_int32()
+        self._check(self.L.mim_set_create_f32(self._ctx, C.c_void_p(_lib.ptr(desc)), step, C.c_void_p(_lib.ptr(kp)),
+                                              int(desc.shape[0]), int(desc.shape[1]), on_dev, C.byref(sid)))
+        if on_dev:
+            # copied on the matcher's stream: kept until that stream has passed the copy
+            ev = torch.cuda.Event()
+            ev.record(mine)
+            self._retired.append((ev, [desc, kp]))
+        self._n_sets = sid.value + 1
+        return sid.value
+
     def add_sets(self, pairs) -> list[int]:
         """Register several sets in one library call (mim_sets_create), as add_set in order: every pair
         (desc, kp) numpy (host) or every pair torch (device), the same rules per pair; all or nothing."""
@@ -296,6 +346,31 @@ class Matcher:
         if k != 2:
             raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
         idx, dist = self.knn_match_hamming_arrays(query, train)
+        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
+                for i in range(idx.shape[0])]
+
+    def knn_match_float_arrays(self, query, train):
+        """BFMatcher(NORM_L2).knnMatch(query, train, k=2) on float32 rows of one dim 1..512 (mim_knn2_l2_f32),
+        as arrays: idx (nq, 2) int32 (-1 absent), dist (nq, 2) float32."""
+        q, t = np.asarray(query), np.asarray(train)
+        if q.dtype != np.float32 or t.dtype != np.float32 or q.ndim != 2 or t.ndim != 2:
+            raise ValueError("knn_match_float: float32 (n, dim) arrays are required")
+        if q.shape[1] != t.shape[1]:
+            raise ValueError(f"knn_match_float: query rows of dim {q.shape[1]}, train rows of dim {t.shape[1]}")
+        q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
+        nq = q.shape[0]
+        idx = np.full((max(nq, 1), 2), -1, np.int32)
+        dist = np.zeros((max(nq, 1), 2), np.float32)
+        self._check(self.L.mim_knn2_l2_f32(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                           t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
+                                           C.c_void_p(dist.ctypes.data)))
+        return idx[:nq], dist[:nq]
+
+    def knn_match_float(self, query, train, k: int = 2):
+        """BFMatcher(NORM_L2).knnMatch(query, train, matches, k=2) on float rows of any dim -> lists of DMatch."""
+        if k != 2:
+            raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
+        idx, dist = self.knn_match_float_arrays(query, train)
         return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
                 for i in range(idx.shape[0])]
 

@@ -19,6 +19,13 @@
  *     the exact-integer i8-MFMA path (v_mfma_i32_32x32x32_i8); any other rows take the fp32 path in
  *     OpenCV's SSE summation order.  Binary rows: xor + popcount, integer throughout.  Every way
  *     indices and distances are bit-identical to the CPU restatement (oracle/, tests/hamming_ref.py).
+ *   - CV_32F rows of any dim 1..512 (SURF/KAZE 64, VGG 48..120, DAISY 200, SuperPoint 256, D2-Net 512,
+ *     and 128-D rows that are not integers: RootSIFT, HardNet, any normalised SIFT) are registered with
+ *     mim_set_create_f32 and matched by the packed-fp32 kernel of csrc/knn_float.hip in OpenCV's
+ *     summation order for that dim, bit-identical to oracle/ too.  mim_set_create still accepts
+ *     non-integer 128-D rows, on a slow one-thread-per-query kernel: callers with such rows should use
+ *     mim_set_create_f32.  NaN and inf rows are outside the contract of every float entry (on x86 the
+ *     sign of a generated NaN decides whether OpenCV's integer compare inserts it).
  */
 #ifndef MIM_H
 #define MIM_H
@@ -130,6 +137,18 @@ mim_status mim_sets_create(struct mim_ctx* ctx, int32_t count, const float* cons
  * MIM_EINVAL for width outside 1..64 or step < width. */
 mim_status mim_set_create_bin(struct mim_ctx* ctx, const uint8_t* desc, int64_t step, const float* kp_xy,
                               int32_t n, int32_t width, int32_t on_device, int32_t* set_id);
+/* A set of n float descriptors of any dim, 1 <= dim <= 512: finite CV_32F rows, row stride `step` bytes
+ * (a multiple of 4, >= 4 * dim, as cv::Mat::step), with their n x 2 float keypoints: what
+ * BFMatcher(NORM_L2) matches for SURF, KAZE, VGG, DAISY, SuperPoint, D2-Net, RootSIFT, HardNet rows.
+ * Ids come from the same sequence as every other set's, and mim_sets_clear / _truncate / _info treat
+ * the set as any other.  Like a binary set it never borrows: rows (each zero-filled to a multiple of 4
+ * floats) and keypoints are copied on the ctx stream into the library's storage; on_device as for
+ * mim_set_create_bin.  Such a set never takes the i8 path, even at dim 128 with integer values.  A
+ * problem's two sets must both be of this kind and of one dim (else MIM_EINVAL at mim_batch_run /
+ * mim_knn2_sets_dev); a batch may mix such problems with 128-D and binary ones.  The mim_group_* and
+ * SIFT entries stay 128-D.  MIM_EINVAL for dim outside 1..512, step < 4 * dim or step % 4 != 0. */
+mim_status mim_set_create_f32(struct mim_ctx* ctx, const float* desc, int64_t step, const float* kp_xy,
+                              int32_t n, int32_t dim, int32_t on_device, int32_t* set_id);
 mim_status mim_sets_clear(struct mim_ctx* ctx);
 /* Drops the sets registered after the first n_keep (ids >= n_keep) and reuses their device storage;
  * the first n_keep keep their ids and layout.  The same rules as mim_sets_clear for work already
@@ -145,11 +164,12 @@ mim_status mim_sets_info(struct mim_ctx* ctx, int32_t* n_sets, int64_t* generati
 /* Debug/test copy-out of set `set_id`: its n float32 descriptor rows (n x 128, row-major) and keypoint
  * positions (n x 2) as the kernels read them, e.g. the device-registered scene scales of
  * mim_sift_scales_sets.  Writes min(n, cap) rows (either output may be NULL); *n_rows = n.  Waits for
- * the ctx stream.  MIM_EINVAL for a binary set (mim_set_create_bin): it has no float rows. */
+ * the ctx stream.  MIM_EINVAL for a binary set (mim_set_create_bin): it has no float rows; and for a
+ * generic float set (mim_set_create_f32): its rows need not have 128 columns. */
 mim_status mim_set_rows(struct mim_ctx* ctx, int32_t set_id, int32_t cap, float* desc, float* kp_xy, int32_t* n_rows);
 
 /* ---- primitive ops, host buffers, synchronous ------------------------------------------------
- * Each primitive call replaces the ctx's "last batch": after mim_knn2_l2 / mim_ratio_filter /
+ * Each primitive call replaces the ctx's "last batch": after mim_knn2_l2 / _l2_f32 / _hamming / mim_ratio_filter /
  * mim_knn2_sets_dev there are no records (mim_batch_results returns none), after
  * mim_find_homography there is that call's one record. */
 /* ≙ BFMatcher(NORM_L2).knnMatch(q, t, matches, 2)            TestsDetector.cpp:36,60
@@ -161,6 +181,11 @@ mim_status mim_knn2_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const fl
  * (first and second place); outputs as mim_knn2_l2. */
 mim_status mim_knn2_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
                             int32_t width, int32_t* idx, float* dist);
+/* ≙ BFMatcher(NORM_L2).knnMatch(q, t, matches, 2) on dense finite CV_32F rows of any dim 1..512, in
+ * OpenCV's summation order for that dim; equal distances keep the lower train index (first and second
+ * place); outputs as mim_knn2_l2.  mim_knn2_l2 itself is unchanged (dim 128 only). */
+mim_status mim_knn2_l2_f32(struct mim_ctx* ctx, const float* q, int32_t nq, const float* t, int32_t nt,
+                           int32_t dim, int32_t* idx, float* dist);
 /* ≙ the ratio-test loop                                     TestsDetector.cpp:66-72
  * Writes queryIdx/trainIdx of survivors in ascending query order; *n_good = goodMatches.size(). */
 mim_status mim_ratio_filter(struct mim_ctx* ctx, const int32_t* idx, const float* dist, int32_t nq,

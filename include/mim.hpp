@@ -30,12 +30,15 @@ namespace mim {
 
 // One view of an ObjectModel: n keypoints (KeyPoint::pt) + their descriptors, either n x 128 CV_32F
 // (SIFT, `descriptors`) or n CV_8U rows of bin_width bytes (ORB, BRIEF, BRISK, FREAK, AKAZE:
-// `bin_descriptors`, matched with NORM_HAMMING) — one of the two, never both.
+// `bin_descriptors`, matched with NORM_HAMMING) — one of the two, never both.  With float_dim nonzero,
+// `descriptors` is n x float_dim CV_32F of any dim 1..512 (SURF, KAZE, VGG, DAISY, SuperPoint, D2-Net,
+// RootSIFT, HardNet), registered with mim_set_create_f32.
 struct View {
     std::vector<Point2f> keypoints;
-    std::vector<float> descriptors;        // row-major n x 128
+    std::vector<float> descriptors;        // row-major n x 128, or n x float_dim
     std::vector<uint8_t> bin_descriptors;  // row-major n x bin_width, dense
     int bin_width = 0;                     // bytes per binary row (1..64); 0: a float view
+    int float_dim = 0;                     // floats per row of a generic float view (1..512); 0: the 128-D path
     int size() const { return (int)keypoints.size(); }
     bool binary() const { return bin_width != 0; }
 };
@@ -106,14 +109,17 @@ class Detector {
     }
 
     // A scene scale's keypoints with its float descriptors (desc, n x 128) or, desc null, its binary
-    // ones (bin_desc, n x bin_width bytes).  A binary model against a float scene (or two widths) is
-    // the library's MIM_EINVAL, thrown as mim::Error.
+    // ones (bin_desc, n x bin_width bytes).  float_dim nonzero: desc is n x float_dim, a generic float
+    // set (mim_set_create_f32).  A binary model against a float scene, two widths, a generic float model
+    // against a 128-D or binary scene, or two float_dims are the library's MIM_EINVAL, thrown as
+    // mim::Error; the Detector stays usable.
     struct ScaledScene {
         const std::vector<Point2f>* kp;
         const std::vector<float>* desc;
         float scale;
         const std::vector<uint8_t>* bin_desc = nullptr;
         int bin_width = 0;
+        int float_dim = 0;
     };
 
     // All (model, scale, view) problems of one scene in one device batch.
@@ -212,11 +218,11 @@ class Detector {
     void register_models(const std::vector<const ModelViews*>& models) {
         std::vector<RegKey> key;
         for (const ModelViews* m : models) {
-            key.push_back({m, m->identity.value(), m->views.size(), nullptr, 0, nullptr, 0, 0, nullptr, 0, 0});
+            key.push_back({m, m->identity.value(), m->views.size(), nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, 0});
             for (const View& v : m->views)
                 key.push_back({nullptr, 0, 0, v.descriptors.data(), v.descriptors.size(),
                                v.keypoints.empty() ? nullptr : &v.keypoints[0].x, v.keypoints.size(), sample(v),
-                               v.bin_descriptors.data(), v.bin_descriptors.size(), v.bin_width});
+                               v.bin_descriptors.data(), v.bin_descriptors.size(), v.bin_width, v.float_dim});
         }
         int64_t gen = -1;
         check(mim_sets_info(ctx_, nullptr, &gen), "mim_sets_info", ctx_);
@@ -237,6 +243,10 @@ class Detector {
                     check(mim_set_create_bin(ctx_, v.bin_descriptors.data(), v.bin_width, kp, v.size(), v.bin_width, 0,
                                              &id),
                           "mim_set_create_bin", ctx_);
+                else if (v.float_dim)
+                    check(mim_set_create_f32(ctx_, v.descriptors.data(), (int64_t)sizeof(float) * v.float_dim, kp,
+                                             v.size(), v.float_dim, 0, &id),
+                          "mim_set_create_f32", ctx_);
                 else
                     check(mim_set_create(ctx_, v.descriptors.data(), kp, v.size(), 128, 0, &id), "mim_set_create", ctx_);
                 reg_ids_[m].push_back(id);
@@ -247,16 +257,19 @@ class Detector {
         reg_n_ = n;
     }
 
-    // FNV-1a over a view's first, middle and last descriptor rows (float or binary) and keypoints
+    // FNV-1a over a view's kind (float_dim) and its first, middle and last descriptor rows (128-D float,
+    // generic float or binary) and keypoints
     static uint64_t sample(const View& v) {
         uint64_t h = 1469598103934665603ull;
         auto mix = [&h](const void* p, size_t bytes) {
             const unsigned char* b = (const unsigned char*)p;
             for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
         };
-        const size_t n = v.keypoints.size(), rows = v.descriptors.size() / 128;
+        const size_t cols = v.float_dim > 0 ? (size_t)v.float_dim : 128;
+        const size_t n = v.keypoints.size(), rows = v.descriptors.size() / cols;
+        mix(&v.float_dim, sizeof v.float_dim);
         for (size_t r : {size_t(0), rows / 2, rows ? rows - 1 : 0})
-            if (r < rows) mix(&v.descriptors[r * 128], 128 * sizeof(float));
+            if (r < rows) mix(&v.descriptors[r * cols], cols * sizeof(float));
         const size_t bw = v.bin_width > 0 ? (size_t)v.bin_width : 0, brows = bw ? v.bin_descriptors.size() / bw : 0;
         for (size_t r : {size_t(0), brows / 2, brows ? brows - 1 : 0})
             if (r < brows) mix(&v.bin_descriptors[r * bw], bw);
@@ -277,6 +290,10 @@ class Detector {
                 check(mim_set_create_bin(ctx_, s.bin_desc->data(), s.bin_width, kp, (int32_t)s.kp->size(), s.bin_width, 0,
                                          &id),
                       "mim_set_create_bin", ctx_);
+            else if (s.float_dim)
+                check(mim_set_create_f32(ctx_, s.desc->data(), (int64_t)sizeof(float) * s.float_dim, kp,
+                                         (int32_t)s.kp->size(), s.float_dim, 0, &id),
+                      "mim_set_create_f32", ctx_);
             else
                 check(mim_set_create(ctx_, s.desc->data(), kp, (int32_t)s.kp->size(), 128, 0, &id), "mim_set_create", ctx_);
             scene_ids.push_back(id);
@@ -330,10 +347,11 @@ class Detector {
         const uint8_t* bin;
         size_t bin_size;
         int bin_width;
+        int float_dim;
         bool operator==(const RegKey& o) const {
             return m == o.m && identity == o.identity && n_views == o.n_views && desc == o.desc &&
                    desc_size == o.desc_size && kp == o.kp && kp_size == o.kp_size && sampled == o.sampled &&
-                   bin == o.bin && bin_size == o.bin_size && bin_width == o.bin_width;
+                   bin == o.bin && bin_size == o.bin_size && bin_width == o.bin_width && float_dim == o.float_dim;
         }
     };
     mim_ctx* ctx_ = nullptr;
