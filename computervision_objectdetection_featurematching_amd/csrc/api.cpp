@@ -26,7 +26,7 @@
 namespace mim {
 void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStream_t st);
 void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const int* seg_start, int n_blocks, Top2* parts,
-                int* dyn_ctr, float kappa, hipStream_t st);
+                int* dyn_ctr, float kappa, float flip_ratio, hipStream_t st);
 int knn_blocks_per_cu();
 void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
 void launch_knn_float(const FltWork* works, int n_works, hipStream_t st);
@@ -214,6 +214,8 @@ struct mim_ctx {
     int knn_grid = 0;      // resident distance-kernel blocks on the device (first batch)
     int n_knn_blocks = 0;  // distance-kernel blocks of the current batch (<= knn_grid)
     bool knn_dyn = false;  // current batch's distance work as 8 per-XCD lists pulled dynamically
+    bool knn_whole = false;  // and every i8 problem as whole sweeps of one split (no tail pieces)
+    int knn_mode = -1;       // the last batch's distance kernel: 0 exact, 1 ratio mode, 2 verdict mode
     hipStream_t cur = nullptr;  // stream the enqueue helpers launch on
     // sampler stream (RansacBufs::s2): the next chunk's getSubset replay beside this chunk's
     // selection kernels (MIM_SAMPLER_STREAM=0: one stream)
@@ -353,6 +355,7 @@ mim_status mim_set_timing(mim_ctx* c, int32_t enable) {
 
 double mim_last_kernel_ms(mim_ctx* c, const char* name) {
     if (!c || !name) return -1;
+    if (!strcmp(name, "knn_mode")) return c->knn_mode;  // not a time: the form the last batch's distance kernel ran in
     auto it = c->last_ms.find(name);
     return it == c->last_ms.end() ? -1 : it->second;
 }
@@ -770,6 +773,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     c->n_works = (int)works.size();
     c->n_knn_blocks = S.n_blocks;
     c->knn_dyn = S.dyn;
+    c->knn_whole = S.dyn;
+    for (int i = 0; i < n; ++i)
+        if (knn_is_i8(in[i]) && S.slots[i].nsplit != 1) c->knn_whole = false;
     if (S.dyn) HIPCHK(c, c->knn_ctr.ensure(8 * sizeof(int)));
     return MIM_OK;
 }
@@ -822,10 +828,20 @@ static float knn_ratio_kappa(float ratio) {
     return kf < 1.f ? kf : 0.f;
 }
 
-static void knn_launch(mim_ctx* c, float kappa = 0.f) {
+// The ratio mode's verdict form (knn.hip, knn2_i8_kernel<2>): a failing query's record carries no valid
+// nearest index, which is sound only where the piece's own verdict is final, so it runs for whole sweeps
+// of one split alone (KnnSchedule::dyn without tail pieces).  MIM_KNN_FLIP=0 (read per launch) keeps the
+// ratio mode.  Returns the ratio for the kernel's own test, 0 = off.
+static float knn_flip_ratio(const mim_ctx* c, float ratio, float kappa) {
+    const char* e = getenv("MIM_KNN_FLIP");
+    if (e && e[0] == '0') return 0.f;
+    return kappa > 0.f && kappa < 1.f && c->knn_whole ? ratio : 0.f;
+}
+
+static void knn_launch(mim_ctx* c, float kappa = 0.f, float flip_ratio = 0.f) {
     const KnnWork* w = c->works.as<KnnWork>();
     launch_knn(c->probs.as<ProbDev>(), w, c->n_works, reinterpret_cast<const int*>(w + c->n_works), c->n_knn_blocks,
-               c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, kappa, c->cur);
+               c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, kappa, flip_ratio, c->cur);
     launch_knn_hamming(c->ham_works.as<HamWork>(), c->n_ham_works, c->cur);
     launch_knn_float(c->flt_works.as<FltWork>(), c->n_flt_works, c->cur);
 }
@@ -835,7 +851,10 @@ static mim_status knn_ratio_locked(mim_ctx* c, int n, float ratio, bool emit_knn
     c->cur = c->stream;
     ev_mark(c, "begin");
     // the ratio test is the only reader of the top-2 unless the knnMatch rows are emitted
-    knn_launch(c, emit_knn ? 0.f : knn_ratio_kappa(ratio));
+    const float kappa = emit_knn ? 0.f : knn_ratio_kappa(ratio);
+    const float flip_ratio = knn_flip_ratio(c, ratio, kappa);
+    c->knn_mode = flip_ratio > 0.f ? 2 : kappa > 0.f ? 1 : 0;
+    knn_launch(c, kappa, flip_ratio);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "knn");
     launch_ratio(c->probs.as<ProbDev>(), n, c->parts.as<Top2>(), ratio, c->good_q.as<int32_t>(), c->good_t.as<int32_t>(),

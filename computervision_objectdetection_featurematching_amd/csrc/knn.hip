@@ -278,6 +278,28 @@ static_assert(kStageChunks * 16 * kThreads == kStage * kTileBytes, "stage split"
 #ifndef MIM_KNN_OCC
 #define MIM_KNN_OCC 4
 #endif
+
+// Verdict mode stores a value doubled with a mark in bit 0: 2 D for a row pushed exactly, 4 R + 3 for a
+// row that was tracked (its R is known, its parity is not): it orders after both exact values it could be.
+// e_hi: the largest D the value can stand for (D itself, or 2 R + 1).
+__device__ __forceinline__ int e_hi(int e) { return e >> 1; }
+// an mn that tracks nothing: 4 kNoTrack + 3 lies above every real value and below INT_MAX
+constexpr int kNoTrack = 1 << 28;
+
+// The ratio argument of the distance kernel: kappa alone for the exact and the ratio mode, (kappa, ratio)
+// for the verdict mode, which evaluates the ratio kernel's own test at the end of the sweep.
+template <int MODE>
+struct KnnRatioArg {
+    using type = float;
+    static __device__ __forceinline__ float kappa(float a) { return a; }
+    static __device__ __forceinline__ float ratio(float) { return 0.f; }
+};
+template <>
+struct KnnRatioArg<2> {
+    using type = float2;
+    static __device__ __forceinline__ float kappa(float2 a) { return a.x; }
+    static __device__ __forceinline__ float ratio(float2 a) { return a.y; }
+};
 //
 // Ratio mode (RATIO, kappa in (0, 1)): the batch path reads the top-2 only through the ratio test
 // k1 < ratio * k2 and i1 where it passes, so a lane pair that fails the test needs less than its exact
@@ -299,10 +321,48 @@ static_assert(kStageChunks * 16 * kThreads == kStage * kTileBytes, "stage split"
 // the true pair does; merged with other splits' pairs the same invariant holds (the minimum is exact,
 // the second too large only behind F).  Equal minima fail the test, so i1 and the rescan's index order do
 // not matter.  Thresholds are on R: D < v is R <= floor((v - 1) / 2).
-template <bool RATIO>
+//
+// Verdict mode (MODE 2; whole sweeps of one split only, so the work item's verdict is final): a failing
+// pair does not take an event for a new minimum either.  A list value is 2 D (exact, pushed with its index)
+// or 4 R + 3 (tracked: the row's R without its parity; D is 2 R or 2 R + 1 = e_hi).  After the event test
+// of a half tile every lane pushes 4 mn + 3 of its smallest row into its two values, unless an event has
+// just pushed that very row exactly, so every value is a row of its own.  This alone gives, per lane and
+// so per pair: (V1) R(Q1) is the smallest R of all rows so far, (V2) e_hi(Q1) >= G1 and e_hi(Q2) >= G2.
+// A refresh calls a pair surely failing when F(2 R(Q1), e_hi(Q2)): F then holds for G1, G2 whatever the
+// parities.  Its limit is the flip limit, every R with not F(2 R, e_hi(Q1)): the rows that could pass
+// against the pair's first value.  Every other pair gets the candidate limit, rows with D < e_hi(Q2).  A lane
+// with a row at or under its limit takes the candidate limit of its current values before the event's
+// pushes (a failing lane that hits is a candidate lane from then on; its partner half stays at the flip
+// limit until the next refresh); after an event limits only fall, to the fresh candidate limit.
+//   (V3) The stored pair surely fails, or R(Q2) = R(G2).  A row ignored under a candidate limit has
+//   D >= e_hi(Q2) >= G2 and changes nothing.  A row W ignored (tracked) under a flip limit taken at Q1r has
+//   F(2 R(W), e_hi(Q1r)); the lane has not hit since, so the stored pair surely failed before W, and after
+//   it: W under Q1 makes Q2 the old Q1 <= Q1r, W between them makes Q2 = W <= the old Q2, and F stays
+//   true as its second argument falls; W above Q2 leaves the pair as it was.  An exact push from another
+//   lane's hit into such a lane is the same three cases.  Two tracked rows of one lane and half tile: only
+//   the smaller is recorded, the other lies above the flip limit as well, same argument.
+//   (V4) If the true pair passes, its nearest row X took an event and Q1 = 2 G1 with X's index: under a
+//   candidate limit D(X) < G2 <= e_hi(Q2); under a flip limit not F(D(X), G2) and G2 <= G1 before X
+//   <= e_hi(Q1r) give not F(2 R(X), e_hi(Q1r)).  No later value lies under it (V2: every value is at least 2 D
+//   of its row).  When X enters, the old Q1, right up to its parity by V1, becomes Q2 in X's lane, or is the
+//   other half's first value (a flip in one half, the old minimum tracked in the other): R(Q2) = R(G2),
+//   also with further rows under the old minimum in the same half tile, which the lane, a candidate
+//   lane by then, pushes as well, or the other half tracks.
+//   (V5) If the stored pair passes with Q1 exact, so does the true one up to Q2's parity: Q2 too large
+//   needs an ignored row under it, which V3 allows only while the stored pair surely fails.
+// End of the sweep: the ratio kernel's own test at the most favourable bounds (Q1 at 2 R, Q2 at e_hi) and at
+// the least favourable (Q1 at e_hi, Q2 at the even value under e_hi: an exact odd Q2 may stand where an
+// unrecorded row of the same R and even parity is the true second).  Failing at the first: the true pair
+// fails by V2, V4; a failing record (k1 = k2) is written.  Passing at both with Q1 exact: passes by V5,
+// i1 by V4.  Anything else (the two differ, or a passing first value is tracked) is marked for
+// knn2_rescan_kernel, which rewrites the record from the fp32 rows.  Padded rows (R = 2^30 - 1) are never
+// under a limit, and their tile caps mn before the shift; a lane half has real rows from the early tiles.
+template <int MODE>  // 0 exact, 1 ratio mode, 2 verdict mode
 __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC = waves per SIMD
     const ProbDev* __restrict__ probs, const KnnWork* __restrict__ works, const int* __restrict__ seg_start,
-    Top2* __restrict__ parts, int* __restrict__ dyn_ctr, float kappa) {
+    Top2* __restrict__ parts, int* __restrict__ dyn_ctr, typename KnnRatioArg<MODE>::type karg) {
+    constexpr bool RATIO = MODE != 0, FLIP = MODE == 2;
+    const float kappa = KnnRatioArg<MODE>::kappa(karg);
     constexpr int QT = kKnnQT;
     // ratio mode: c(q) of the work item's queries behind the two stage buffers (read once per stage)
     constexpr int kCqOff = 2 * kStage * kLdsTile;
@@ -379,11 +439,13 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
     // threshold after an insertion.  Ratio mode: never above the one set at the last refresh (a
     // failing pair keeps its lower threshold through other lanes' events, see the proof above)
     auto event_threshold = [&](int u) {
-        if (RATIO) T[u] = min(T[u], below_threshold(pair_second(st[u], o1c[u], o2c[u])));
+        if (FLIP) T[u] = min(T[u], below_threshold(e_hi(pair_second(st[u], o1c[u], o2c[u]))));
+        else if (RATIO) T[u] = min(T[u], below_threshold(pair_second(st[u], o1c[u], o2c[u])));
         else T[u] = late_threshold(st[u], o1c[u], o2c[u]);
     };
     auto push = [&](int u, int v, int idx) {
-        if (RATIO) sel_push_r(st[u], v, idx);
+        if (FLIP) sel_push_r(st[u], v << 1, idx);  // exact values are stored as 2 D
+        else if (RATIO) sel_push_r(st[u], v, idx);
         else sel_push(st[u], v, idx);
     };
 
@@ -483,9 +545,9 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
         for (int u = 0; u < QT; ++u) {
             LaneSel t;
             // D = (key - 2^28) >> 7, row = key & 127 (with the lane's 4h, which the lists store without)
-            t.m1 = k1[u] == 0xFFFFFFFFu ? INT_MAX : (int)(k1[u] - (1u << 28)) >> 7;
+            t.m1 = k1[u] == 0xFFFFFFFFu ? INT_MAX : ((int)(k1[u] - (1u << 28)) >> 7) << (FLIP ? 1 : 0);
             t.i1 = k1[u] == 0xFFFFFFFFu ? INT_MAX : tile * 64 + (int)(k1[u] & 127) - 4 * h;
-            t.m2 = k2[u] == 0xFFFFFFFFu ? INT_MAX : (int)(k2[u] - (1u << 28)) >> 7;
+            t.m2 = k2[u] == 0xFFFFFFFFu ? INT_MAX : ((int)(k2[u] - (1u << 28)) >> 7) << (FLIP ? 1 : 0);
             t.i2 = RATIO || k2[u] == 0xFFFFFFFFu ? INT_MAX : tile * 64 + (int)(k2[u] & 127) - 4 * h;
             st[u] = RATIO ? sel_merge_r(st[u], t) : sel_merge(st[u], t);
         }
@@ -519,6 +581,10 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
 #pragma unroll
             for (int u = 0; u < QT; ++u) {
                 if (bm[u] != 0) {
+                    // verdict mode: a lane that hits takes the candidate limit of its current values before
+                    // its rows are pushed (a surely failing lane becomes a candidate lane: the rows between
+                    // its flip limit and its second value now count; a candidate lane's limit only falls)
+                    if (FLIP) T[u] = mn[u] <= T[u] ? below_threshold(e_hi(pair_second(st[u], o1c[u], o2c[u]))) : T[u];
                     // per row of a hit group: one compare (the ballot) and, if some lane has the row
                     // under its threshold, an unconditional insertion in every lane (the lane lists
                     // stay the exact top-2 of the rows pushed, a superset of the filtered ones); the
@@ -547,10 +613,12 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                                 }
                                 const int pos1 = (k1 & 3) + 8 * ((k1 >> 2) & 1) + 16 * i;
                                 push(u, dval(k1 >> 3, (pw >> pos1) & 1), row0 + pos1);
+                                if (FLIP) mn[u] = (k1 >> 3) == mn[u] ? kNoTrack : mn[u];
                                 event_threshold(u);
                                 if (__builtin_expect(__ballot((k2 >> 3) <= T[u]) == 0, 1)) continue;
                                 const int pos2 = (k2 & 3) + 8 * ((k2 >> 2) & 1) + 16 * i;
                                 push(u, dval(k2 >> 3, (pw >> pos2) & 1), row0 + pos2);
+                                if (FLIP) mn[u] = (k2 >> 3) == mn[u] ? kNoTrack : mn[u];
                                 event_threshold(u);
                             }
                             // rows in index order (keyed: only those after the second key, all of which
@@ -562,14 +630,35 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                                                  (MIM_KNN_EVENT != 1 || !keyed || ((acc[u][8 * i + g] << 3) | g) > k2));
 #pragma unroll
                             for (int g = 8 * i; g < 8 * i + 8; ++g) {
-                                if (__builtin_expect(hm[g - 8 * i] != 0, 0))
+                                if (__builtin_expect(hm[g - 8 * i] != 0, 0)) {
                                     push(u, dval(acc[u][g], (pw >> ((g & 3) + 8 * (g >> 2))) & 1),
                                          row0 + (g & 3) + 8 * (g >> 2));
+                                    // verdict mode: the lane's smallest row is in its list now, exactly
+                                    if (FLIP) mn[u] = acc[u][g] == mn[u] ? kNoTrack : mn[u];
+                                }
                             }
                         }
                     }
                     event_threshold(u);
                 }
+            }
+        }
+        if (FLIP) {
+            // the half tile's smallest row of the lane enters its list as a tracked value, without an event
+            // and after the events: a lane whose smallest row has just been pushed exactly has no mn left
+            // (kNoTrack), so no row is counted twice.  Three VALU per column tile: v_lshl_or_b32,
+            // v_med3_i32, v_min_i32.  The padded tile (R = 2^30 - 1 would overflow the shift) caps mn first,
+            // in a branch of its own (the asm keeps it a branch).
+            if (__builtin_expect(!keyed, 0)) {
+                asm volatile("; padded tile");
+#pragma unroll
+                for (int u = 0; u < QT; ++u) mn[u] = min(mn[u], kNoTrack);
+            }
+#pragma unroll
+            for (int u = 0; u < QT; ++u) {
+                const int tv = (mn[u] << 2) | 3;
+                st[u].m2 = med3_i32(st[u].m1, st[u].m2, tv);  // = max(m1, min(m2, tv)) as m1 <= m2
+                st[u].m1 = min(st[u].m1, tv);
             }
         }
     };
@@ -646,7 +735,18 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                 const auto b = __builtin_amdgcn_permlane32_swap(st[u].m2, st[u].m2, false, false);
                 o1c[u] = (tid & 32) ? (int)a[0] : (int)a[1];
                 o2c[u] = (tid & 32) ? (int)b[0] : (int)b[1];
-                if (RATIO) {
+                if (FLIP) {
+                    // surely failing: the test fails for the smallest first and the largest second value
+                    // the pair's two values can stand for.  Its limit is the flip limit: a row passes against
+                    // the first value only if (float)(2 R + p + c) < tf, so R <= (ceil(tf) - c) >> 1 holds
+                    // every such row (d^2 < 2^24 is exact in float); never above the rows under the minimum
+                    const int e1 = pair_first(st[u], o1c[u]), e2 = pair_second(st[u], o1c[u], o2c[u]);
+                    const int c = cqv[u];
+                    const float tf = kappa * (float)(e_hi(e1) + c);
+                    const bool fail = e2 != INT_MAX && (float)((e_hi(e1) & ~1) + c) >= kappa * (float)(e_hi(e2) + c);
+                    const int flip = min(((int)ceilf(tf) - c) >> 1, below_threshold(e_hi(e1)));
+                    T[u] = fail ? flip : below_threshold(e_hi(e2));
+                } else if (RATIO) {
                     // the pair's two smallest D, both halves fresh: exact or failing (invariant above)
                     const int q1 = pair_first(st[u], o1c[u]), q2 = pair_second(st[u], o1c[u], o2c[u]);
                     const int c = cqv[u];
@@ -688,11 +788,25 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
             // c(q), read here rather than held in a register for the whole sweep
             const int qq = ((const gint*)P->q.norm)[(size_t)(q >> 6) * kNormWords + 128 + (q & 63)];
             Top2 t;
-            const int d1 = m.m1 + qq, d2 = m.m2 + qq;  // exact d^2 = D + c(q) (< 2^23)
+            // exact d^2 = D + c(q) (< 2^23); verdict mode: the largest d^2 the values can stand for
+            const int d1 = (FLIP ? e_hi(m.m1) : m.m1) + qq, d2 = (FLIP ? e_hi(m.m2) : m.m2) + qq;
             t.k1 = m.i1 == INT_MAX ? FLT_MAX : sqrtf((float)d1);
             t.k2 = m.i2 == INT_MAX ? FLT_MAX : sqrtf((float)d2);
             t.i1 = m.i1;
             t.i2 = m.i2;
+            if (FLIP && m.i2 != INT_MAX) {
+                // the ratio kernel's test at the bounds of what the two values can stand for: the first at
+                // its lower bound (a tracked 2 R + 1 may be 2 R), the second at its upper bound and at the
+                // even value under it (a row of the same R and even parity may have gone by unrecorded)
+                const float ratio = KnnRatioArg<MODE>::ratio(karg);
+                const int h1 = d1, l1 = max(h1 - (m.m1 & 1), 0), h2 = d2, l2 = max(h2 - (e_hi(m.m2) & 1), 0);
+                const bool p_opt = sqrtf((float)l1) < ratio * sqrtf((float)h2);
+                const bool p_pes = sqrtf((float)h1) < ratio * sqrtf((float)l2);
+                t.k1 = sqrtf((float)h1);
+                t.k2 = sqrtf((float)l2);
+                if (!p_opt) t.k2 = t.k1;                                 // fails whatever the parities: k1 >= k2
+                else if (!p_pes || (m.m1 & 1)) t.i2 = kRescan;           // undecided here: the exact rescan decides
+            }
             // d^2 >= 4e6: distinct integers may share a key (sqrt class), where the lower index
             // wins: rescan exactly.  Below, equal keys mean equal d^2, already in index order.
             // (ratio mode: the test reads the two smallest keys as values, and those are the keys of
@@ -975,20 +1089,26 @@ void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStrea
 // device) and only the matching kernel does the work, so no host round trip is needed.
 int knn_blocks_per_cu() {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, knn2_i8_kernel<false>, kThreads, 0) != hipSuccess) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, knn2_i8_kernel<0>, kThreads, 0) != hipSuccess) nb = 1;
     return nb;
 }
 
 void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const int* seg_start, int n_blocks,
-                Top2* parts, int* dyn_ctr, float kappa, hipStream_t st) {
+                Top2* parts, int* dyn_ctr, float kappa, float flip_ratio, hipStream_t st) {
     if (n_works <= 0) return;
     if (dyn_ctr) (void)hipMemsetAsync(dyn_ctr, 0, 8 * sizeof(int), st);
     // kappa in (0, 1): the ratio-mode instantiation (its parts feed ratio_compact_kernel only and
     // mark nothing for the rescan); otherwise the exact top-2
-    if (kappa > 0.f && kappa < 1.f) {
-        knn2_i8_kernel<true><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, kappa);
+    // flip_ratio > 0 (whole sweeps of one split only): the verdict-mode instantiation, whose records are
+    // final verdicts; the few it leaves undecided are marked for the rescan
+    if (kappa > 0.f && kappa < 1.f && flip_ratio > 0.f) {
+        knn2_i8_kernel<2><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr,
+                                                         make_float2(kappa, flip_ratio));
+        knn2_rescan_kernel<<<n_works, 256, 0, st>>>(probs, works, parts);
+    } else if (kappa > 0.f && kappa < 1.f) {
+        knn2_i8_kernel<1><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, kappa);
     } else {
-        knn2_i8_kernel<false><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, 0.f);
+        knn2_i8_kernel<0><<<n_blocks, kThreads, 0, st>>>(probs, works, seg_start, parts, dyn_ctr, 0.f);
         knn2_rescan_kernel<<<n_works, 256, 0, st>>>(probs, works, parts);
     }
     knn2_f32_kernel<<<std::min(n_works, 2048), 256, 0, st>>>(probs, works, parts, n_works);

@@ -406,7 +406,9 @@ mim_status mim_group_scene_points(mim_group* g, int32_t scene, float* out_xy, in
 /* Per-kernel device time (ms) summed over the batches since the last result fetch, measured with
  * HIP events on the stream each kernel ran on.  names: "knn", "ratio", "attempt", "chain",
  * "check", "sample", "score" (the bound kernel; "hypo"/"score"/"select" in the MIM_RANSAC_EXACT
- * reference mode), "cand", "exact", "select" (the replay), "refine".  Returns -1 if unknown. */
+ * reference mode), "cand", "exact", "select" (the replay), "refine".  Returns -1 if unknown.
+ * "knn_mode" is not a time: the form the last batch's i8 distance kernel ran in (0 exact top-2, 1 ratio
+ * mode, 2 verdict mode; -1 before the first batch), whether or not timing is on. */
 double mim_last_kernel_ms(struct mim_ctx* ctx, const char* name);
 mim_status mim_set_timing(struct mim_ctx* ctx, int32_t enable);
 

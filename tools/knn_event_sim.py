@@ -1,13 +1,22 @@
-"""Count the distance kernel's late-tile insertion events on the CPU (numpy), exact mode against ratio mode.
+"""Count the distance kernel's late-tile insertion events on the CPU (numpy): exact mode, ratio mode and
+verdict mode (flip-only events).
 
-usage: python tools/knn_event_sim.py [--config c4] [--scene 0] [--queries 2000] [--ratio 0.9]
+usage: python tools/knn_event_sim.py [--config c4] [--scene 0] [--queries 2048] [--offset 0] [--stride 0] [--ratio 0.9]
+
+The sample is whole 64-query waves: --queries of them in all, from query --offset on, every --stride-th
+wave (0: spread evenly over the whole query set, the default, which weights planted and unplanted queries
+as the batch does; 1: contiguous).  On C3/C4 the planted matches are the first 2,000 queries of a model, so
+a contiguous sample from 0 describes the planted fifth of the batch only.
 
 Replays one problem of a config with the kernel's layout (csrc/knn.hip): rows of a 32-row block go to
 the lane halves ((row % 32) >> 2) & 1, the first 256 rows are early, a stage is 256 rows, the limit of a
 lane is fixed inside a 32-row half tile.  An event is a row at or under its lane's limit.  Exact mode:
 limit = 2nd smallest of the pair's four values.  Ratio mode: a pair that fails d1^2 >= kappa d2^2 at the
-stage's refresh has limit = its minimum.  Prints events per query and the share of (64-query wave, half
-tile) visits with at least one event.
+stage's refresh has limit = its minimum.  Verdict mode: such a pair has limit kappa x its minimum (only a
+row that could make it pass), records a new minimum without an event, and a lane that takes an event goes
+on with the candidate limit.  Prints events per query, the share of (64-query wave, half tile) visits with
+at least one event, and the number of sampled queries whose brute-force verdict changes when either d^2
+moves by one (the queries verdict mode may have to rescan).
 """
 import argparse
 import os
@@ -21,8 +30,8 @@ from computervision_objectdetection_featurematching_amd.synthetic import make_co
 BIG = np.int64(2**40)
 
 
-def replay(d, kappa):
-    """d: (nq, nt) exact squared distances.  kappa = 0: exact mode."""
+def replay(d, kappa, flip=False):
+    """d: (nq, nt) exact squared distances (nq a multiple of 64).  kappa = 0: exact mode."""
     nq, nt = d.shape
     m = np.full((2, 2, nq), BIG)  # [half][rank][query]
     o = np.full((2, 2, nq), BIG)
@@ -48,8 +57,16 @@ def replay(d, kappa):
                 q1, q2 = np.minimum(m[h, 0], o[h, 0]), second(h)
                 fail = (kappa > 0) & (q1.astype(np.float32) >= np.float32(kappa) * q2.astype(np.float32))
                 lim[h] = np.where(fail, q1, q2 + (kappa == 0))  # exact mode keeps ties (index order)
+                if flip:  # rows that pass against the minimum: (float)d < kappa (float)q1
+                    fl = np.ceil(np.float32(kappa) * q1.astype(np.float32)).astype(np.int64)
+                    lim[h] = np.where(fail, np.minimum(fl, q1), q2)
         cur = lim.copy()
         hit = np.zeros(nq, bool)
+        if flip and late:  # a lane with a row under its limit takes the candidate limit first
+            for h in range(2):
+                jh = [j for j in range(b0, min(b0 + 32, nt)) if ((j % 32) >> 2) & 1 == h]
+                if jh:
+                    cur[h] = np.where(d[:, jh].min(1) < cur[h], second(h), cur[h])
         for j in range(b0, min(b0 + 32, nt)):
             h = ((j % 32) >> 2) & 1
             on = d[:, j] < cur[h] if late else np.ones(nq, bool)
@@ -57,9 +74,11 @@ def replay(d, kappa):
                 events += on
                 hit |= on
             push(h, d[:, j], on)
+            if flip and late:  # the minimum without an event (the sim keeps no parities: a plain push)
+                push(h, d[:, j], ~on)
         if late:
             for h in range(2):
-                lim[h] = np.minimum(lim[h], second(h) + (kappa == 0))
+                lim[h] = np.minimum(cur[h] if flip else lim[h], second(h) + (kappa == 0))
             w = hit[: nq // 64 * 64].reshape(-1, 64).any(1)
             visits += w.size
             hits += int(w.sum())
@@ -70,19 +89,38 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c4")
     ap.add_argument("--scene", type=int, default=0)
-    ap.add_argument("--queries", type=int, default=2000)
+    ap.add_argument("--queries", type=int, default=2048)
+    ap.add_argument("--offset", type=int, default=0)
+    ap.add_argument("--stride", type=int, default=0, help="in 64-query waves; 0 = spread over the whole set")
     ap.add_argument("--ratio", type=float, default=0.9)
     a = ap.parse_args()
     ds = make_config_dataset(a.config, scene_ids=[a.scene])
-    q = ds.model_desc[0][: a.queries].astype(np.float64)
+    allq = ds.model_desc[0]
+    waves = np.arange(a.offset // 64, len(allq) // 64)
+    n_w = max(1, a.queries // 64)
+    if a.stride > 0:
+        waves = waves[:: a.stride][:n_w]
+    else:
+        waves = waves[np.unique(np.linspace(0, len(waves) - 1, min(n_w, len(waves))).astype(int))]
+    q = allq[(waves[:, None] * 64 + np.arange(64)[None, :]).ravel()].astype(np.float64)
     t = ds.scene_desc[0].astype(np.float64)
     d = np.rint((q * q).sum(1)[:, None] + (t * t).sum(1)[None, :] - 2.0 * (q @ t.T)).astype(np.int64)
     r = float(np.float32(a.ratio))
     kappa = r * r * (1 + 2.0**-18) * (1 + 2.0**-20)
-    for name, k in (("exact", 0.0), ("ratio", kappa)):
-        ev, share = replay(d, k)
-        print(f"{a.config} scene {a.scene} {d.shape[0]} x {d.shape[1]} {name:5s}: {ev:.2f} events per query, "
+    print(f"{a.config} scene {a.scene}: {len(waves)} waves of 64 queries, waves {waves[0]} .. {waves[-1]} of {len(allq) // 64}")
+    for name, k, flip in (("exact", 0.0, False), ("ratio", kappa, False), ("verdict", kappa, True)):
+        ev, share = replay(d, k, flip)
+        print(f"{a.config} scene {a.scene} {d.shape[0]} x {d.shape[1]} {name:7s}: {ev:.2f} events per query, "
               f"{100 * share:.1f} % of wave x half-tile visits take the event path")
+    s2 = np.sort(d, axis=1)[:, :2]
+
+    def good(d1, d2):
+        return np.sqrt(np.float32(d1)) < np.float32(a.ratio) * np.sqrt(np.float32(d2))
+
+    g = good(s2[:, 0], s2[:, 1])
+    dep = (good(np.maximum(s2[:, 0] - 1, 0), s2[:, 1]) != g) | (good(s2[:, 0], s2[:, 1] - 1) != g) | \
+          (good(s2[:, 0] + 1, s2[:, 1]) != g) | (good(s2[:, 0], s2[:, 1] + 1) != g)
+    print(f"{int(g.sum())} of {len(g)} sampled queries pass; {int(dep.sum())} verdicts change when either d^2 moves by one")
 
 
 if __name__ == "__main__":
