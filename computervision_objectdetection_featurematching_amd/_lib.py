@@ -27,6 +27,7 @@ EXPORTS = [
     "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_group_scene_images_run", "mim_group_scene_points",
     "mim_set_create_bin", "mim_knn2_hamming",
     "mim_set_create_f32", "mim_knn2_l2_f32",
+    "mim_batch_run_filter", "mim_match_cross_sets",
 ]
 
 
@@ -113,6 +114,8 @@ def load():
     L.mim_ratio_filter.argtypes = [vp, i32p, f32p, i32, C.c_float, i32p, i32p, C.POINTER(C.c_int32)]
     L.mim_find_homography.argtypes = [vp, f32p, f32p, i32, C.c_double, i32, C.c_double, f64p, u8p]
     L.mim_batch_run.argtypes = [vp, C.POINTER(Problem), i32, C.POINTER(Params)]
+    L.mim_batch_run_filter.argtypes = [vp, C.POINTER(Problem), i32, C.POINTER(Params), i32]
+    L.mim_match_cross_sets.argtypes = [vp, i32, i32, i32p, f32p]
     L.mim_batch_results.argtypes = [vp, vp]
     L.mim_batch_results_dev.argtypes = [vp]
     L.mim_batch_results_dev.restype = vp
@@ -152,7 +155,8 @@ def load():
     for name in ("mim_group_shard", "mim_group_create", "mim_group_size", "mim_group_uses_rccl", "mim_group_set_create",
                  "mim_group_scene_batch_run", "mim_group_results", "mim_group_scene_images_run",
                  "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_set_create_bin",
-                 "mim_knn2_hamming", "mim_set_create_f32", "mim_knn2_l2_f32"):
+                 "mim_knn2_hamming", "mim_set_create_f32", "mim_knn2_l2_f32", "mim_batch_run_filter",
+                 "mim_match_cross_sets"):
         getattr(L, name).restype = C.c_int32
     for name in ("mim_ctx_create", "mim_ctx_set_stream", "mim_synchronize", "mim_set_create", "mim_sets_create", "mim_sets_clear",
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",

@@ -29,7 +29,12 @@ void launch_knn(const ProbDev* probs, const KnnWork* works, int n_works, const i
                 int* dyn_ctr, float kappa, float flip_ratio, hipStream_t st);
 int knn_blocks_per_cu();
 void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
+void launch_knn_hamming_cross(const HamCrossWork* works, int n_works, uint32_t* colmin, long long n_col,
+                              hipStream_t st);
 void launch_knn_float(const FltWork* works, int n_works, hipStream_t st);
+void launch_cross(const ProbDev* probs, const CrossDev* cross, int n_probs, const Top2* parts, float ratio, int filter,
+                  int32_t* good_q, int32_t* good_t, float4* pts, int* n_good, int32_t* match_idx, float* match_dist,
+                  hipStream_t st);
 void launch_ratio(const ProbDev* probs, int n_probs, const Top2* parts, float ratio, int32_t* good_q,
                   int32_t* good_t, float4* pts, int* n_good, int32_t* knn_idx, float* knn_dist,
                   hipStream_t st);
@@ -184,6 +189,13 @@ struct mim_ctx {
     std::vector<ProbDev> h_probs;
     int n_ham_works = 0;  // Hamming work items of the current batch (its binary problems)
     int n_flt_works = 0;  // generic-float work items of the current batch
+    // cross-check batches (mim_batch_run_filter): the one-pass Hamming kernel's work items
+    // and column minima, and the per-problem table of where the reverse nearest rows are
+    DevBuf ham_cross_works, colmin, cross_tab;
+    int n_ham_cross_works = 0;
+    long long n_colmin = 0;  // entries of colmin over the batch's fused binary problems
+    int knn_cross = 0;       // how the last batch found the reverse neighbours: 0 not, 1 second sweep, 2 fused
+    int last_filter = 0;     // the last mim_batch_run_filter's filter, for its re-run
     int n_cu = 0;         // compute units of the device (first batch)
     int n_works = 0;  // distance segments of the current batch (works, then the per-block segment starts)
     std::vector<long long> h_good_off;
@@ -315,7 +327,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -355,6 +367,7 @@ mim_status mim_set_timing(mim_ctx* c, int32_t enable) {
 
 double mim_last_kernel_ms(mim_ctx* c, const char* name) {
     if (!c || !name) return -1;
+    if (!strcmp(name, "knn_cross")) return c->knn_cross;  // nor this: how the last batch found the reverse neighbours
     if (!strcmp(name, "knn_mode")) return c->knn_mode;  // not a time: the form the last batch's distance kernel ran in
     auto it = c->last_ms.find(name);
     return it == c->last_ms.end() ? -1 : it->second;
@@ -668,7 +681,11 @@ static KnnSchedKnobs knn_knobs() {
 // block indices with equal (index % 8) so they share one XCD's L2 under round-robin dispatch
 // (speed only).
 // ---------------------------------------------------------------------------------------------
-static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, int max_iters) {
+// filter != 0 (cross-check): the n problems are followed by their shadows (knn_cross_problems), which
+// take part in the distance stage only; ProbDev i < n is still problem i.
+static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int n_user, int max_iters, int filter = 0) {
+    const mim_problem* problems = user_problems;
+    int n = n_user;
     mim_status fs = flush_preps(c);  // the sets' device tiles and flags, before ProbDev copies them
     if (fs != MIM_OK) return fs;
     if (c->knn_grid == 0) {  // resident distance-kernel blocks: CUs x blocks per CU (occupancy query)
@@ -698,8 +715,30 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
                         T.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
         if (Q.fdim != T.fdim)
             return fail(c, MIM_EINVAL, "problem %d: generic float sets of different dims (%d and %d)", i, Q.fdim, T.fdim);
+        if (filter != 0 && Q.d.n >= (1 << 18))  // the query set is the reverse direction's train set
+            return fail(c, MIM_EINVAL, "problem %d: query set of %d rows exceeds OpenCV's 2^18 limit under a cross-check "
+                                       "filter", i, Q.d.n);
         in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
         in[i].fdim = Q.fdim;
+    }
+    // cross-check: the shadows join the problem list (binary problems under the fused kernel have none)
+    std::vector<int> shadow_of;
+    std::vector<mim_problem> ext;
+    c->knn_cross = 0;
+    if (filter != 0) {
+        const char* e = getenv("MIM_CROSS_FUSED");  // read per launch; 0: binary problems take shadow sweeps too
+        const bool fused = !(e && e[0] == '0');
+        in = knn_cross_problems(in, fused, shadow_of);
+        ext.assign(user_problems, user_problems + n_user);
+        ext.resize(in.size());
+        bool any_fused = false;
+        for (int i = 0; i < n_user; ++i) {
+            if (shadow_of[i] >= 0) ext[shadow_of[i]] = mim_problem{user_problems[i].train_set, user_problems[i].query_set};
+            else any_fused = true;
+        }
+        problems = ext.data();
+        n = (int)in.size();
+        c->knn_cross = any_fused ? 2 : 1;
     }
     const KnnSchedule S = knn_schedule(in, c->knn_grid, c->n_cu, max_iters, knn_knobs());
     c->h_probs.assign(n, ProbDev{});
@@ -720,17 +759,41 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     HIPCHK(c, c->probs.ensure(sizeof(ProbDev) * std::max(n, 1)));
     HIPCHK(c, c->works.ensure(sizeof(KnnWork) * std::max<size_t>(works.size(), 1) + sizeof(int) * seg.size()));
     HIPCHK(c, c->parts.ensure(sizeof(Top2) * std::max<long long>(part, 1)));
+    // cross-check: a fused binary problem's column minima colmin[nt], the others' shadows
+    std::vector<CrossDev> cross;
+    std::vector<long long> col_off;
+    long long n_col = 0;
+    if (filter != 0) {
+        col_off.assign(n_user, -1);
+        for (int i = 0; i < n_user; ++i)
+            if (shadow_of[i] < 0) {
+                col_off[i] = n_col;
+                n_col += std::max(in[i].nt, 1);
+            }
+        HIPCHK(c, c->colmin.ensure(sizeof(uint32_t) * std::max<long long>(n_col, 1)));
+        HIPCHK(c, c->cross_tab.ensure(sizeof(CrossDev) * std::max(n_user, 1)));
+        cross.resize(n_user);
+        for (int i = 0; i < n_user; ++i)
+            cross[i] = CrossDev{shadow_of[i] < 0 ? c->colmin.as<uint32_t>() + col_off[i] : nullptr, shadow_of[i], 0};
+    }
+    c->n_colmin = n_col;
     // the Hamming pieces with their pointers (parts is sized above)
     std::vector<HamWork> ham;
+    std::vector<HamCrossWork> hamx;
     ham.reserve(S.ham.size());
     for (const HamPiece& hp : S.ham) {
         const ProbDev& P = c->h_probs[hp.problem];
         const int wdw = c->sets[problems[hp.problem].query_set].bin_pad / 4;
-        ham.push_back(HamWork{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
-                              c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, P.q.n, hp.q0, hp.r0,
-                              hp.r1, wdw, 0});
+        const HamWork hw{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
+                         c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, P.q.n, hp.q0, hp.r0,
+                         hp.r1, wdw, 0};
+        if (filter != 0 && hp.problem < n_user && shadow_of[hp.problem] < 0)
+            hamx.push_back(HamCrossWork{hw, c->colmin.as<uint32_t>() + col_off[hp.problem]});
+        else
+            ham.push_back(hw);
     }
     if (!ham.empty()) HIPCHK(c, c->ham_works.ensure(sizeof(HamWork) * ham.size()));
+    if (!hamx.empty()) HIPCHK(c, c->ham_cross_works.ensure(sizeof(HamCrossWork) * hamx.size()));
     // and the generic-float pieces
     std::vector<FltWork> flt;
     flt.reserve(S.flt.size());
@@ -749,8 +812,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
     // the device tables are rewritten in stream order (after the previous batch's kernels)
     const size_t pb = sizeof(ProbDev) * n, wb = sizeof(KnnWork) * works.size(), sb = sizeof(int) * seg.size();
     const size_t hb = sizeof(HamWork) * ham.size(), fb = sizeof(FltWork) * flt.size();
+    const size_t xb = sizeof(HamCrossWork) * hamx.size(), cb = sizeof(CrossDev) * cross.size();
     char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb + fb, &st));
+    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb + fb + xb + cb, &st));
     memcpy(st, c->h_probs.data(), pb);
     memcpy(st + pb, works.data(), wb);
     memcpy(st + pb + wb, seg.data(), sb);
@@ -764,12 +828,21 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* problems, int n, i
         memcpy(st + pb + wb + sb + hb, flt.data(), fb);
         HIPCHK(c, hipMemcpyAsync(c->flt_works.p, st + pb + wb + sb + hb, fb, hipMemcpyHostToDevice, c->stream));
     }
+    if (xb) {
+        memcpy(st + pb + wb + sb + hb + fb, hamx.data(), xb);
+        HIPCHK(c, hipMemcpyAsync(c->ham_cross_works.p, st + pb + wb + sb + hb + fb, xb, hipMemcpyHostToDevice, c->stream));
+    }
+    if (cb) {
+        memcpy(st + pb + wb + sb + hb + fb + xb, cross.data(), cb);
+        HIPCHK(c, hipMemcpyAsync(c->cross_tab.p, st + pb + wb + sb + hb + fb + xb, cb, hipMemcpyHostToDevice, c->stream));
+    }
     c->n_ham_works = (int)ham.size();
+    c->n_ham_cross_works = (int)hamx.size();
     c->n_flt_works = (int)flt.size();
     HIPCHK(c, c->stage.release_after(c->stream));
-    c->h_good_off.resize(n);
-    for (int i = 0; i < n; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
-    c->last_n = n;
+    c->h_good_off.resize(n_user);
+    for (int i = 0; i < n_user; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
+    c->last_n = n_user;
     c->n_works = (int)works.size();
     c->n_knn_blocks = S.n_blocks;
     c->knn_dyn = S.dyn;
@@ -843,23 +916,34 @@ static void knn_launch(mim_ctx* c, float kappa = 0.f, float flip_ratio = 0.f) {
     launch_knn(c->probs.as<ProbDev>(), w, c->n_works, reinterpret_cast<const int*>(w + c->n_works), c->n_knn_blocks,
                c->parts.as<Top2>(), c->knn_dyn ? c->knn_ctr.as<int>() : nullptr, kappa, flip_ratio, c->cur);
     launch_knn_hamming(c->ham_works.as<HamWork>(), c->n_ham_works, c->cur);
+    launch_knn_hamming_cross(c->ham_cross_works.as<HamCrossWork>(), c->n_ham_cross_works, c->colmin.as<uint32_t>(),
+                             c->n_colmin, c->cur);
     launch_knn_float(c->flt_works.as<FltWork>(), c->n_flt_works, c->cur);
 }
 
 // distance + ratio kernels of the batch's problems
-static mim_status knn_ratio_locked(mim_ctx* c, int n, float ratio, bool emit_knn) {
+// filter != 0: the cross-check compaction instead of the ratio kernel, behind the exact distance kernel
+// (the reverse top-1 and the mutuality test need exact nearest indices, which the ratio and verdict modes
+// do not keep); match_idx / match_dist: mim_match_cross_sets' per-query rows
+static mim_status knn_ratio_locked(mim_ctx* c, int n, float ratio, bool emit_knn, int filter = 0,
+                                   int32_t* match_idx = nullptr, float* match_dist = nullptr) {
     c->cur = c->stream;
     ev_mark(c, "begin");
     // the ratio test is the only reader of the top-2 unless the knnMatch rows are emitted
-    const float kappa = emit_knn ? 0.f : knn_ratio_kappa(ratio);
+    const float kappa = emit_knn || filter != 0 ? 0.f : knn_ratio_kappa(ratio);
     const float flip_ratio = knn_flip_ratio(c, ratio, kappa);
     c->knn_mode = flip_ratio > 0.f ? 2 : kappa > 0.f ? 1 : 0;
     knn_launch(c, kappa, flip_ratio);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "knn");
-    launch_ratio(c->probs.as<ProbDev>(), n, c->parts.as<Top2>(), ratio, c->good_q.as<int32_t>(), c->good_t.as<int32_t>(),
-                 c->pts.as<float4>(), c->n_good.as<int>(), emit_knn ? c->knn_idx.as<int32_t>() : nullptr,
-                 emit_knn ? c->knn_dist.as<float>() : nullptr, c->cur);
+    if (filter != 0)
+        launch_cross(c->probs.as<ProbDev>(), c->cross_tab.as<CrossDev>(), n, c->parts.as<Top2>(), ratio, filter,
+                     c->good_q.as<int32_t>(), c->good_t.as<int32_t>(), c->pts.as<float4>(), c->n_good.as<int>(),
+                     match_idx, match_dist, c->cur);
+    else
+        launch_ratio(c->probs.as<ProbDev>(), n, c->parts.as<Top2>(), ratio, c->good_q.as<int32_t>(), c->good_t.as<int32_t>(),
+                     c->pts.as<float4>(), c->n_good.as<int>(), emit_knn ? c->knn_idx.as<int32_t>() : nullptr,
+                     emit_knn ? c->knn_dist.as<float>() : nullptr, c->cur);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "ratio");
     return MIM_OK;
@@ -1509,21 +1593,23 @@ extern "C" {
 
 }  // extern "C"
 
-static mim_status batch_run_locked(mim_ctx* c, const mim_problem* problems, int32_t n, const mim_params* params) {
+static mim_status batch_run_locked(mim_ctx* c, const mim_problem* problems, int32_t n, const mim_params* params,
+                                   int filter) {
     HIPCHK(c, hipSetDevice(c->device));
     c->last_problems.assign(problems, problems + n);
     c->last_params = *params;
+    c->last_filter = filter;
     c->last_gen = c->sets_gen;
     c->last_fh = false;
     if (n == 0) { c->last_n = 0; return MIM_OK; }
-    mim_status s = build_tables(c, problems, n, std::max(params->max_iters, 1));
+    mim_status s = build_tables(c, problems, n, std::max(params->max_iters, 1), filter);
     if (s != MIM_OK) return s;
     RansacBufs b;
     RansacParams rp;
     long long flag_per = 0;
     s = ransac_prepare(c, n, params, b, rp, flag_per);
     if (s != MIM_OK) return s;
-    s = knn_ratio_locked(c, n, params->ratio, false);
+    s = knn_ratio_locked(c, n, params->ratio, false, filter);
     if (s != MIM_OK) return s;
     return ransac_enqueue_range(c, 0, n, b, rp, flag_per, 0);
 }
@@ -1548,7 +1634,7 @@ static mim_status finish_batch_locked(mim_ctx* c, std::vector<mim_result>& res) 
         if (s != MIM_OK) return s;
         const std::vector<mim_problem> probs = c->last_problems;
         const mim_params prm = c->last_params;
-        s = batch_run_locked(c, probs.data(), (int32_t)probs.size(), &prm);
+        s = batch_run_locked(c, probs.data(), (int32_t)probs.size(), &prm, c->last_filter);
         if (s != MIM_OK) return s;
     }
 }
@@ -1561,7 +1647,45 @@ mim_status mim_batch_run(mim_ctx* c, const mim_problem* problems, int32_t n, con
     mim_status s = check_params(c, params);
     if (s != MIM_OK) return s;
     std::lock_guard<std::mutex> lk(c->mu);
-    return batch_run_locked(c, problems, n, params);
+    return batch_run_locked(c, problems, n, params, MIM_FILTER_RATIO);
+}
+
+mim_status mim_batch_run_filter(mim_ctx* c, const mim_problem* problems, int32_t n, const mim_params* params,
+                                int32_t filter) {
+    if (!c) return MIM_EINVAL;
+    if (n < 0 || (n > 0 && !problems)) return fail(c, MIM_EINVAL, "batch_run_filter: bad arguments");
+    if (filter < MIM_FILTER_RATIO || filter > MIM_FILTER_RATIO_CROSS)
+        return fail(c, MIM_EINVAL, "batch_run_filter: filter must be 0 (ratio), 1 (cross) or 2 (ratio and cross), got %d",
+                    filter);
+    mim_status s = check_params(c, params);
+    if (s != MIM_OK) return s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return batch_run_locked(c, problems, n, params, filter);
+}
+
+mim_status mim_match_cross_sets(mim_ctx* c, int32_t query_set, int32_t train_set, int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (!idx || !dist) return fail(c, MIM_EINVAL, "match_cross_sets: null output");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    mim_problem pr{query_set, train_set};
+    mim_status s = build_tables(c, &pr, 1, 1, MIM_FILTER_CROSS);
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    if (s != MIM_OK) return s;
+    const int nq = c->h_probs[0].q.n;
+    HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * std::max(nq, 1)));
+    HIPCHK(c, c->knn_dist.ensure(sizeof(float) * std::max(nq, 1)));
+    s = knn_ratio_locked(c, 1, 0.f, false, MIM_FILTER_CROSS, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>());
+    if (s != MIM_OK) return s;
+    if (nq > 0) {
+        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * nq, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ev_collect(c);
+    return MIM_OK;
 }
 
 mim_status mim_batch_results(mim_ctx* c, mim_result* out) {

@@ -1012,6 +1012,87 @@ __global__ __launch_bounds__(1024) void ratio_compact_kernel(const ProbDev* __re
 }
 
 // ------------------------------------------------------------------------------------------------
+// Cross-check filter (BFMatcher(norm, crossCheck = true).match) in the shape of
+// ratio_compact_kernel: per query, merge the forward splits, look up the reverse nearest row of its
+// nearest train row i1 (the shadow problem's partials at row i1, or the fused Hamming kernel's column
+// minimum), keep the pair iff that is the query itself (filter 1), and the ratio test holds as well
+// (filter 2); then the same ordered compaction, point gather and n_good.  match_idx / match_dist
+// (mim_match_cross_sets): per query the matched train row or -1, its distance or FLT_MAX.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void cross_compact_kernel(const ProbDev* __restrict__ probs,
+                                                            const CrossDev* __restrict__ cross,
+                                                            const Top2* __restrict__ parts, float ratio,
+                                                            int filter, int32_t* __restrict__ good_q,
+                                                            int32_t* __restrict__ good_t,
+                                                            float4* __restrict__ pts,
+                                                            int* __restrict__ n_good,
+                                                            int32_t* __restrict__ match_idx,
+                                                            float* __restrict__ match_dist) {
+    __shared__ int wsum[16];
+    __shared__ int wbase[17];
+    const ProbDev* P = probs + blockIdx.x;
+    const CrossDev X = cross[blockIdx.x];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nq = P->q.n;
+    int running = 0;
+    for (int base = 0; base < nq; base += 1024) {
+        const int q = base + tid;
+        T2 m{FLT_MAX, INT_MAX, FLT_MAX, INT_MAX};
+        if (q < nq) {
+            for (int sp = 0; sp < P->nsplit; ++sp) {
+                const Top2 t = parts[P->part_off + (long long)sp * P->q_pad + q];
+                m = top2_merge(m, t.k1, t.i1);
+                m = top2_merge(m, t.k2, t.i2);
+            }
+        }
+        const float k1 = m.k1, k2 = m.k2;
+        const int i1 = m.i1, i2 = m.i2;
+        int back = -1;  // the lowest query row nearest to train row i1
+        if (q < nq && i1 != INT_MAX) {
+            if (X.colmin) {
+                const uint32_t key = X.colmin[i1];
+                back = key == 0xFFFFFFFFu ? -1 : (int)(key & 0x3FFFFu);
+            } else {
+                const ProbDev* S = probs + X.shadow;
+                T2 r{FLT_MAX, INT_MAX, FLT_MAX, INT_MAX};
+                for (int sp = 0; sp < S->nsplit; ++sp) {
+                    const Top2 t = parts[S->part_off + (long long)sp * S->q_pad + i1];
+                    r = top2_merge(r, t.k1, t.i1);
+                    r = top2_merge(r, t.k2, t.i2);
+                }
+                back = r.i1 == INT_MAX ? -1 : r.i1;
+            }
+        }
+        const bool good = q < nq && i1 != INT_MAX && back == q && (filter == 1 || (i2 != INT_MAX && k1 < ratio * k2));
+        if (q < nq && match_idx) {
+            match_idx[q] = good ? i1 : -1;
+            match_dist[q] = good ? k1 : FLT_MAX;
+        }
+        const unsigned long long bal = __ballot(good);
+        const int within = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        if (tid == 0) {
+            int acc = 0;
+            for (int i = 0; i < 16; ++i) { wbase[i] = acc; acc += wsum[i]; }
+            wbase[16] = acc;
+        }
+        __syncthreads();
+        if (good) {
+            const long long o = P->good_off + running + wbase[wave] + within;
+            good_q[o] = q;
+            good_t[o] = i1;
+            const float2 a = P->q.kp[q], b = P->t.kp[i1];
+            pts[o] = make_float4(a.x, a.y, b.x, b.y);
+        }
+        running += wbase[16];
+        __syncthreads();
+    }
+    if (tid == 0) n_good[blockIdx.x] = running;
+}
+
+// ------------------------------------------------------------------------------------------------
 // knnMatch rows alone (mim_knn2_l2 / mim_knn2_sets_dev): merge the train splits of every query of
 // one problem, one thread per query over the whole grid (no ratio test, no compaction).
 // ------------------------------------------------------------------------------------------------
@@ -1130,6 +1211,14 @@ void launch_ratio(const ProbDev* probs, int n_probs, const Top2* parts, float ra
     if (n_probs > 0)
         ratio_compact_kernel<<<n_probs, 1024, 0, st>>>(probs, parts, ratio, good_q, good_t, pts, n_good,
                                                        knn_idx, knn_dist);
+}
+
+void launch_cross(const ProbDev* probs, const CrossDev* cross, int n_probs, const Top2* parts, float ratio, int filter,
+                  int32_t* good_q, int32_t* good_t, float4* pts, int* n_good, int32_t* match_idx, float* match_dist,
+                  hipStream_t st) {
+    if (n_probs > 0)
+        cross_compact_kernel<<<n_probs, 1024, 0, st>>>(probs, cross, parts, ratio, filter, good_q, good_t, pts, n_good,
+                                                       match_idx, match_dist);
 }
 
 }  // namespace mim

@@ -48,6 +48,7 @@ struct KnnSchedProblem {
     int n_tiles;  // train tiles (SetDev::n_tiles)
     bool bin;     // binary descriptors: the Hamming work list, not the i8 schedule
     int fdim = 0; // generic float rows of this dim (mim_set_create_f32): the float work list, not the i8 schedule
+    bool shadow = false;  // reverse direction of a cross-check problem (knn_cross_problems): distance stage only
 };
 
 // problems of the i8 schedule: neither binary nor generic-float
@@ -318,6 +319,11 @@ inline void knn_layout_offsets(const std::vector<KnnSchedProblem>& in, int max_i
         KnnSchedSlot& P = S.slots[i];
         P.part_off = part;
         part += (long long)P.nsplit * P.q_pad;
+        if (in[i].shadow) {  // partials only: no good-match or iteration capacity
+            P.good_off = good;
+            P.it_off = it;
+            continue;
+        }
         P.good_off = good;
         good += (std::max(in[i].nq, 1) + 31) & ~31;  // 32-aligned: the MFMA bound's point tiles
         P.it_off = it;
@@ -325,6 +331,28 @@ inline void knn_layout_offsets(const std::vector<KnnSchedProblem>& in, int max_i
     }
     S.part = part;
     S.good = good;
+}
+
+// Cross-check batches: the problems followed by their shadows, a shadow being the same
+// pair with the two sets swapped (nq x nt becomes nt x nq), which goes through the distance stage like any
+// problem of its kind and so leaves the reverse top-2 partials [nsplit][pad(nt)].  shadow_of[i] is
+// problem i's shadow in the returned list, -1 where it has none: a binary problem under `fused`, whose
+// reverse nearest rows come from the one-pass kernel's column minima (hamming.hip) instead.
+inline std::vector<KnnSchedProblem> knn_cross_problems(const std::vector<KnnSchedProblem>& in, bool fused,
+                                                       std::vector<int>& shadow_of) {
+    std::vector<KnnSchedProblem> out(in);
+    shadow_of.assign(in.size(), -1);
+    for (size_t i = 0; i < in.size(); ++i) {
+        if (in[i].bin && fused) continue;
+        KnnSchedProblem s = in[i];
+        s.nq = in[i].nt;
+        s.nt = in[i].nq;
+        s.n_tiles = (in[i].nq + 63) / 64;  // SetDev::n_tiles of the query set
+        s.shadow = true;
+        shadow_of[i] = (int)out.size();
+        out.push_back(s);
+    }
+    return out;
 }
 
 // G: resident distance-kernel blocks of the device.

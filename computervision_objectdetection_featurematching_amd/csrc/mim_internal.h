@@ -72,6 +72,21 @@ struct HamWork {
     int pad_;
 };
 
+// Work item of the one-pass Hamming cross kernel (knn2_hamming_cross_kernel): the same piece, and the
+// problem's column minima colmin[nt], packed keys distance << 18 | query row, 0xFFFFFFFF before any.
+struct HamCrossWork {
+    HamWork w;
+    uint32_t* colmin;
+};
+
+// Cross-check table of one problem (cross_compact_kernel): where the reverse nearest
+// row of a train row is found.
+struct CrossDev {
+    const uint32_t* colmin;  // fused Hamming kernel's column minima [nt]; null: the shadow's partials
+    int shadow;              // the shadow's ProbDev (the two sets swapped), -1 with colmin
+    int pad_;
+};
+
 // Generic float sets (knn_float.hip, DESIGN.md "Float descriptors of any dimension").  Such a set's
 // SetDev has f32 = its rows at a stride of `dp` floats (dim rounded up to a multiple of 4, zero filled;
 // zero rows up to the next multiple of kFltRowPad past the last row), kp and n; frag, norm and flags are

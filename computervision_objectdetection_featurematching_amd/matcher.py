@@ -56,6 +56,7 @@ class Matcher:
         self.device = device
         self._borrowed = []  # (set id, tensors) the registered sets read until they are dropped (mim.h)
         self._n_sets = 0
+        self._set_rows = {}  # set id -> rows, of the sets registered through this object (match_cross_sets)
         self.sets_generation = 0  # bumped whenever registered sets are dropped
         self._retired = []   # (event on the matcher stream, tensors) kept alive until the event completes
 
@@ -126,6 +127,7 @@ class Matcher:
         if on_dev:
             self._borrowed.append((sid.value, [desc, kp]))
         self._n_sets = sid.value + 1
+        self._set_rows[sid.value] = int(desc.shape[0])
         return sid.value
 
     def add_binary_set(self, desc_u8, kp) -> int:
@@ -175,6 +177,7 @@ class Matcher:
             ev.record(mine)
             self._retired.append((ev, [desc, kp]))
         self._n_sets = sid.value + 1
+        self._set_rows[sid.value] = int(desc.shape[0])
         return sid.value
 
     def add_float_set(self, desc, kp) -> int:
@@ -225,6 +228,7 @@ class Matcher:
             ev.record(mine)
             self._retired.append((ev, [desc, kp]))
         self._n_sets = sid.value + 1
+        self._set_rows[sid.value] = int(desc.shape[0])
         return sid.value
 
     def add_sets(self, pairs) -> list[int]:
@@ -274,6 +278,7 @@ class Matcher:
             for sid, d, k in zip(ids, descs, kps):
                 self._borrowed.append((sid, [d, k]))
         self._n_sets = first.value + n
+        self._set_rows.update(zip(ids, (int(r) for r in rows)))
         return ids
 
     @property
@@ -293,6 +298,7 @@ class Matcher:
             self._retired.append((ev, gone))
         self._borrowed = [(sid, ts) for sid, ts in self._borrowed if sid < keep]
         self._n_sets = min(self._n_sets, keep)
+        self._set_rows = {sid: r for sid, r in self._set_rows.items() if sid < keep}
         self.sets_generation += 1
 
     def clear_sets(self):
@@ -543,13 +549,23 @@ class Matcher:
         return H.reshape(3, 3), mask
 
     # ---- fused batch ----------------------------------------------------------------------
-    def match_batch_async(self, problems, params: Params | None = None):
+    FILTERS = {"ratio": 0, "cross": 1, "ratio+cross": 2}  # MIM_FILTER_* (mim_batch_run_filter)
+
+    def match_batch_async(self, problems, params: Params | None = None, filter: str = "ratio"):
+        """Enqueue one batch.  filter: "ratio" (Lowe's ratio test, mim_batch_run), "cross" (mutual nearest
+        neighbours, BFMatcher(norm, crossCheck=True).match; params.ratio is ignored) or "ratio+cross" (both)."""
+        if filter not in self.FILTERS:
+            raise ValueError(f"match_batch: filter must be one of {sorted(self.FILTERS)}, got {filter!r}")
         params = params or default_params()
         # an (n, 2) int32 array is mim_problem[n] as it is (no per-problem ctypes objects: ~1 us each)
         arr = problems if isinstance(problems, np.ndarray) else np.asarray(list(problems), np.int32)
         arr = np.ascontiguousarray(arr, np.int32).reshape(-1, 2)
-        self._check(self.L.mim_batch_run(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr),
-                                         C.byref(params)))
+        if filter == "ratio":
+            self._check(self.L.mim_batch_run(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr),
+                                             C.byref(params)))
+        else:
+            self._check(self.L.mim_batch_run_filter(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr),
+                                                    C.byref(params), self.FILTERS[filter]))
         return len(arr)
 
     def batch_results(self, n: int) -> np.ndarray:
@@ -597,9 +613,23 @@ class Matcher:
         self._check(st)
         return offs, buf[:total].copy()
 
-    def match_batch(self, problems, params: Params | None = None) -> np.ndarray:
-        n = self.match_batch_async(problems, params)
+    def match_batch(self, problems, params: Params | None = None, filter: str = "ratio") -> np.ndarray:
+        n = self.match_batch_async(problems, params, filter)
         return self.batch_results(n)
+
+    def match_cross_sets(self, qset: int, tset: int, nq: int | None = None):
+        """BFMatcher(norm, crossCheck=True).match on two registered sets of one kind (mim_match_cross_sets):
+        (idx int32[nq], dist float32[nq]), idx[i] the train row matched to query i or -1, dist[i] its distance
+        or FLT_MAX.  nq: the query set's rows, needed only for a set this object did not register itself."""
+        if nq is None:
+            nq = self._set_rows.get(int(qset))
+        if nq is None:
+            raise ValueError(f"match_cross_sets: the row count of set {qset} is not known here: pass nq")
+        idx = np.full(max(nq, 1), -1, np.int32)
+        dist = np.zeros(max(nq, 1), np.float32)
+        self._check(self.L.mim_match_cross_sets(self._ctx, int(qset), int(tset), C.c_void_p(idx.ctypes.data),
+                                                C.c_void_p(dist.ctypes.data)))
+        return idx[:nq], dist[:nq]
 
     def knn_sets_dev(self, qset: int, tset: int, idx_dev, dist_dev):
         self._check(self.L.mim_knn2_sets_dev(self._ctx, qset, tset, C.c_void_p(_lib.ptr(idx_dev)),

@@ -202,6 +202,23 @@ mim_status mim_find_homography(struct mim_ctx* ctx, const float* src_xy, const f
  * without waiting.  Results stay on the device until fetched. */
 mim_status mim_batch_run(struct mim_ctx* ctx, const mim_problem* problems, int32_t n,
                          const mim_params* params);
+/* The same batch with another way to pick the good matches (BFMatcher's two standard filters):
+ *   MIM_FILTER_RATIO        Lowe's ratio test, exactly mim_batch_run (the same launches and records);
+ *   MIM_FILTER_CROSS        BFMatcher(norm, crossCheck = true).match: query i is matched to its nearest
+ *                           train row s(i), the lowest-indexed one at the least distance, iff i is in turn the
+ *                           lowest-indexed query row at the least distance from s(i); params->ratio is ignored;
+ *   MIM_FILTER_RATIO_CROSS  both: the intersection of the two lists.
+ * Distances are the DMatch::distance values of the sets' kind; survivors keep ascending query order.
+ * Records, mim_batch_problem_detail, mim_batch_inlier_points, mim_batch_results_copy and the re-run
+ * after MIM_STREAM_SHORT work as for any batch (the re-run keeps the filter).  Under filters 1 and 2 the
+ * query set is also a train set (the reverse direction), so a query set of 2^18 rows or more is
+ * MIM_EINVAL here, beside the train-side check; any other filter value is MIM_EINVAL.  The mim_group_*
+ * entries, GroupDetector, the Python pipeline and the OpenCV adapter stay ratio-only. */
+#define MIM_FILTER_RATIO 0
+#define MIM_FILTER_CROSS 1
+#define MIM_FILTER_RATIO_CROSS 2
+mim_status mim_batch_run_filter(struct mim_ctx* ctx, const mim_problem* problems, int32_t n,
+                                const mim_params* params, int32_t filter);
 /* Waits, then copies the n mim_result records to host memory.  A problem that ran out of RNG
  * draws (MIM_STREAM_SHORT) makes the ctx grow its stream (x8, up to 2^30 draws) and re-run the
  * batch first; that needs the batch's sets intact (no mim_sets_clear since mim_batch_run), else
@@ -238,6 +255,14 @@ mim_status mim_batch_inlier_points(struct mim_ctx* ctx, const float* scales, flo
  * Asynchronous.  idx_dev / dist_dev: device buffers of 2*nq int32 / float32. */
 mim_status mim_knn2_sets_dev(struct mim_ctx* ctx, int32_t query_set, int32_t train_set,
                              int32_t* idx_dev, float* dist_dev);
+
+/* ---- cross-check matching alone on registered sets (BFMatcher(norm, true).match) ---------------
+ * Synchronous.  idx / dist: host buffers of nq entries: idx[i] is query i's matched train row or -1,
+ * dist[i] its distance, FLT_MAX where idx[i] is -1.  Any pair of sets mim_knn2_sets_dev accepts (all four
+ * kinds), with the same pairing errors, and a query set below 2^18 rows.  Like the other primitives it
+ * leaves the ctx without a batch (mim_batch_results returns no records). */
+mim_status mim_match_cross_sets(struct mim_ctx* ctx, int32_t query_set, int32_t train_set, int32_t* idx,
+                                float* dist);
 
 /* ---- feature extraction either side of the matcher ---------------------------
  * cv::KeyPoint without class_id; octave packed as OpenCV packs it (octave & 255 | layer << 8 |
@@ -408,7 +433,10 @@ mim_status mim_group_scene_points(mim_group* g, int32_t scene, float* out_xy, in
  * "check", "sample", "score" (the bound kernel; "hypo"/"score"/"select" in the MIM_RANSAC_EXACT
  * reference mode), "cand", "exact", "select" (the replay), "refine".  Returns -1 if unknown.
  * "knn_mode" is not a time: the form the last batch's i8 distance kernel ran in (0 exact top-2, 1 ratio
- * mode, 2 verdict mode; -1 before the first batch), whether or not timing is on. */
+ * mode, 2 verdict mode; -1 before the first batch), whether or not timing is on.  Nor is "knn_cross": how
+ * the last batch found the reverse nearest neighbours of a cross-check filter (0 not at all, 1 a second
+ * sweep with the two sets swapped, 2 the one-pass Hamming kernel for every binary problem); the cross
+ * compaction's time is under "ratio". */
 double mim_last_kernel_ms(struct mim_ctx* ctx, const char* name);
 mim_status mim_set_timing(struct mim_ctx* ctx, int32_t enable);
 

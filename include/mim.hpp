@@ -88,6 +88,15 @@ class Detector {
 
     mim_params& params() { return params_; }
     mim_ctx* ctx() { return ctx_; }
+    // How the good matches of every later call are picked (mim_batch_run_filter): MIM_FILTER_RATIO (the
+    // default, Lowe's ratio test), MIM_FILTER_CROSS (mutual nearest neighbours, BFMatcher's crossCheck) or
+    // MIM_FILTER_RATIO_CROSS (both).  GroupDetector stays ratio-only.
+    void set_filter(int32_t filter) {
+        if (filter < MIM_FILTER_RATIO || filter > MIM_FILTER_RATIO_CROSS)
+            throw Error(MIM_EINVAL, "Detector::set_filter: filter must be 0, 1 or 2");
+        filter_ = filter;
+    }
+    int32_t filter() const { return filter_; }
 
     // Per-view outcome of the last call (same order as the views).
     const std::vector<mim_result>& last_results() const { return results_; }
@@ -317,7 +326,11 @@ class Detector {
                 }
         results_.assign(probs.size(), mim_result{});
         if (probs.empty()) return;
-        check(mim_batch_run(ctx_, probs.data(), (int32_t)probs.size(), &params_), "mim_batch_run", ctx_);
+        if (filter_ == MIM_FILTER_RATIO)
+            check(mim_batch_run(ctx_, probs.data(), (int32_t)probs.size(), &params_), "mim_batch_run", ctx_);
+        else
+            check(mim_batch_run_filter(ctx_, probs.data(), (int32_t)probs.size(), &params_, filter_),
+                  "mim_batch_run_filter", ctx_);
         check(mim_batch_results(ctx_, results_.data()), "mim_batch_results", ctx_);
         // :87-94 inlier scene points of the accepted problems (:74, :79, :81, :84), divided by the scale
         // when it is not 1, gathered on the device in batch order (one copy); model m's problems are
@@ -356,6 +369,7 @@ class Detector {
     };
     mim_ctx* ctx_ = nullptr;
     mim_params params_;
+    int32_t filter_ = MIM_FILTER_RATIO;
     std::vector<mim_result> results_;
     std::vector<RegKey> reg_key_;  // the models whose views are the ctx's first reg_n_ sets
     std::vector<std::vector<int32_t>> reg_ids_;
