@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -32,6 +33,9 @@ void launch_knn_hamming(const HamWork* works, int n_works, hipStream_t st);
 void launch_knn_hamming_cross(const HamCrossWork* works, int n_works, uint32_t* colmin, long long n_col,
                               hipStream_t st);
 void launch_knn_float(const FltWork* works, int n_works, hipStream_t st);
+void launch_knn_topk_hamming(const TopkHamWork* works, int n_works, int k, hipStream_t st);
+void launch_knn_topk_float(const TopkFltWork* works, int n_works, int k, hipStream_t st);
+void launch_knn_topk_merge(const TopkProb* probs, int n_probs, int max_nq, int k, hipStream_t st);
 void launch_cross(const ProbDev* probs, const CrossDev* cross, int n_probs, const Top2* parts, float ratio, int filter,
                   int32_t* good_q, int32_t* good_t, float4* pts, int* n_good, int32_t* match_idx, float* match_dist,
                   hipStream_t st);
@@ -194,6 +198,9 @@ struct mim_ctx {
     DevBuf ham_cross_works, colmin, cross_tab;
     int n_ham_cross_works = 0;
     long long n_colmin = 0;  // entries of colmin over the batch's fused binary problems
+    // top-k entries (mim_knn_batch_dev): partial lists, work items and the merge's problem table
+    DevBuf topk_parts, topk_ham_works, topk_flt_works, topk_probs;
+    int topk_splits = 0;  // the most train splits of a problem of the last such call
     int knn_cross = 0;       // how the last batch found the reverse neighbours: 0 not, 1 second sweep, 2 fused
     int last_filter = 0;     // the last mim_batch_run_filter's filter, for its re-run
     int n_cu = 0;         // compute units of the device (first batch)
@@ -327,7 +334,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -368,6 +375,7 @@ mim_status mim_set_timing(mim_ctx* c, int32_t enable) {
 double mim_last_kernel_ms(mim_ctx* c, const char* name) {
     if (!c || !name) return -1;
     if (!strcmp(name, "knn_cross")) return c->knn_cross;  // nor this: how the last batch found the reverse neighbours
+    if (!strcmp(name, "knn_topk_splits")) return c->topk_splits;  // nor this: the last top-k call's most train splits
     if (!strcmp(name, "knn_mode")) return c->knn_mode;  // not a time: the form the last batch's distance kernel ran in
     auto it = c->last_ms.find(name);
     return it == c->last_ms.end() ? -1 : it->second;
@@ -676,6 +684,44 @@ static KnnSchedKnobs knn_knobs() {
     return k;
 }
 
+// resident distance-kernel blocks: CUs x blocks per CU (occupancy query), once per ctx
+static mim_status device_limits(mim_ctx* c) {
+    if (c->knn_grid == 0) {
+        hipDeviceProp_t prop;
+        HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
+        c->knn_grid = std::max(1, prop.multiProcessorCount * std::max(1, knn_blocks_per_cu()));
+        c->n_cu = std::max(1, prop.multiProcessorCount);
+    }
+    return MIM_OK;
+}
+
+// The pairing rules of a problem's two sets (mim_batch_run and every entry that takes mim_problem records):
+// both of one kind, one width or dim, a train set below 2^18 rows; cross: the query set is a train set too.
+static mim_status check_problem_sets(mim_ctx* c, int i, int qs, int ts, bool cross) {
+    if (qs < 0 || qs >= (int)c->sets.size() || ts < 0 || ts >= (int)c->sets.size())
+        return fail(c, MIM_EINVAL, "problem %d: bad set id (%d, %d)", i, qs, ts);
+    if (c->sets[ts].d.n >= (1 << 18))  // BFMatcher::knnMatchImpl: train rows < 1 << 18 (IMGIDX_SHIFT)
+        return fail(c, MIM_EINVAL, "problem %d: train set of %d rows exceeds OpenCV's 2^18 limit", i,
+                    c->sets[ts].d.n);
+    const SetRec &Q = c->sets[qs], &T = c->sets[ts];
+    if ((Q.bin_pad != 0) != (T.bin_pad != 0))
+        return fail(c, MIM_EINVAL, "problem %d: set %d holds %s descriptors and set %d %s ones", i, qs,
+                    Q.bin_pad ? "binary" : "float", ts, T.bin_pad ? "binary" : "float");
+    if (Q.bin_width != T.bin_width)
+        return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
+                    T.bin_width);
+    if ((Q.fdim != 0) != (T.fdim != 0))
+        return fail(c, MIM_EINVAL, "problem %d: set %d holds %s rows and set %d %s ones", i, qs,
+                    Q.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)", ts,
+                    T.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
+    if (Q.fdim != T.fdim)
+        return fail(c, MIM_EINVAL, "problem %d: generic float sets of different dims (%d and %d)", i, Q.fdim, T.fdim);
+    if (cross && Q.d.n >= (1 << 18))  // the query set is the reverse direction's train set
+        return fail(c, MIM_EINVAL, "problem %d: query set of %d rows exceeds OpenCV's 2^18 limit under a cross-check "
+                                   "filter", i, Q.d.n);
+    return MIM_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Problem table + distance work list (knn_schedule.h).  Work items of one problem are placed at
 // block indices with equal (index % 8) so they share one XCD's L2 under round-robin dispatch
@@ -688,36 +734,14 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     int n = n_user;
     mim_status fs = flush_preps(c);  // the sets' device tiles and flags, before ProbDev copies them
     if (fs != MIM_OK) return fs;
-    if (c->knn_grid == 0) {  // resident distance-kernel blocks: CUs x blocks per CU (occupancy query)
-        hipDeviceProp_t prop;
-        HIPCHK(c, hipGetDeviceProperties(&prop, c->device));
-        c->knn_grid = std::max(1, prop.multiProcessorCount * std::max(1, knn_blocks_per_cu()));
-        c->n_cu = std::max(1, prop.multiProcessorCount);
-    }
+    fs = device_limits(c);
+    if (fs != MIM_OK) return fs;
     std::vector<KnnSchedProblem> in(n);
     for (int i = 0; i < n; ++i) {
         const int qs = problems[i].query_set, ts = problems[i].train_set;
-        if (qs < 0 || qs >= (int)c->sets.size() || ts < 0 || ts >= (int)c->sets.size())
-            return fail(c, MIM_EINVAL, "problem %d: bad set id (%d, %d)", i, qs, ts);
-        if (c->sets[ts].d.n >= (1 << 18))  // BFMatcher::knnMatchImpl: train rows < 1 << 18 (IMGIDX_SHIFT)
-            return fail(c, MIM_EINVAL, "problem %d: train set of %d rows exceeds OpenCV's 2^18 limit", i,
-                        c->sets[ts].d.n);
+        const mim_status ps = check_problem_sets(c, i, qs, ts, filter != 0);
+        if (ps != MIM_OK) return ps;
         const SetRec &Q = c->sets[qs], &T = c->sets[ts];
-        if ((Q.bin_pad != 0) != (T.bin_pad != 0))
-            return fail(c, MIM_EINVAL, "problem %d: set %d holds %s descriptors and set %d %s ones", i, qs,
-                        Q.bin_pad ? "binary" : "float", ts, T.bin_pad ? "binary" : "float");
-        if (Q.bin_width != T.bin_width)
-            return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
-                        T.bin_width);
-        if ((Q.fdim != 0) != (T.fdim != 0))
-            return fail(c, MIM_EINVAL, "problem %d: set %d holds %s rows and set %d %s ones", i, qs,
-                        Q.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)", ts,
-                        T.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
-        if (Q.fdim != T.fdim)
-            return fail(c, MIM_EINVAL, "problem %d: generic float sets of different dims (%d and %d)", i, Q.fdim, T.fdim);
-        if (filter != 0 && Q.d.n >= (1 << 18))  // the query set is the reverse direction's train set
-            return fail(c, MIM_EINVAL, "problem %d: query set of %d rows exceeds OpenCV's 2^18 limit under a cross-check "
-                                       "filter", i, Q.d.n);
         in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
         in[i].fdim = Q.fdim;
     }
@@ -1147,6 +1171,177 @@ mim_status mim_knn2_sets_dev(mim_ctx* c, int32_t query_set, int32_t train_set, i
     c->last_gen = -1;
     c->last_fh = false;
     return MIM_OK;
+}
+
+// Top-k: the work lists of knn_hamming_plan / knn_float_plan over the call's problems, the
+// distance kernels of knn_topk.hip into the top-k partials, then the merge into the caller's rows.  128-D
+// sets go through the float kernel on their f32 rows (no prep is needed or flushed).  With the lock held.
+static mim_status knn_topk_locked(mim_ctx* c, const mim_problem* problems, int n, int k, int32_t* idx_dev,
+                                  float* dist_dev) {
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    if (k < 1 || k > MIM_KNN_MAX_K) return fail(c, MIM_EINVAL, "knn: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
+    if (n < 0 || (n > 0 && !problems)) return fail(c, MIM_EINVAL, "knn: bad arguments");
+    if (n == 0) return MIM_OK;
+    mim_status s = device_limits(c);
+    if (s != MIM_OK) return s;
+    std::vector<KnnSchedProblem> in(n);
+    long long rows = 0;
+    int max_nq = 0;
+    for (int i = 0; i < n; ++i) {
+        const int qs = problems[i].query_set, ts = problems[i].train_set;
+        s = check_problem_sets(c, i, qs, ts, false);
+        if (s != MIM_OK) return s;
+        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
+        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
+        in[i].fdim = Q.bin_pad ? 0 : Q.fdim ? Q.fdim : kDim;  // 128-D sets: the float work list at dim 128
+        rows += Q.d.n;
+        max_nq = std::max(max_nq, Q.d.n);
+    }
+    if (rows > 0 && (!idx_dev || !dist_dev)) return fail(c, MIM_EINVAL, "knn: null output");
+    KnnSchedule S;
+    S.slots.assign(n, KnnSchedSlot{});
+    knn_hamming_plan(in, c->n_cu, S);
+    knn_float_plan(in, c->n_cu, S);
+    const KnnTopkLayout Lo = knn_topk_offsets(in, S.slots, k);
+    c->topk_splits = 0;
+    for (const KnnSchedSlot& sl : S.slots) c->topk_splits = std::max(c->topk_splits, sl.nsplit);
+    HIPCHK(c, c->topk_parts.ensure(sizeof(TopkEnt) * std::max<long long>(Lo.part, 1)));
+    HIPCHK(c, c->topk_probs.ensure(sizeof(TopkProb) * n));
+    TopkEnt* parts = c->topk_parts.as<TopkEnt>();
+    std::vector<TopkProb> probs(n);
+    for (int i = 0; i < n; ++i)
+        probs[i] = TopkProb{parts + Lo.part_off[i], idx_dev + Lo.out_off[i], dist_dev + Lo.out_off[i], in[i].nq,
+                            S.slots[i].nsplit, S.slots[i].q_pad, 0};
+    std::vector<TopkHamWork> ham;
+    ham.reserve(S.ham.size());
+    for (const HamPiece& hp : S.ham) {
+        const SetRec &Q = c->sets[problems[hp.problem].query_set], &T = c->sets[problems[hp.problem].train_set];
+        ham.push_back(TopkHamWork{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag),
+                                  parts + Lo.part_off[hp.problem] + (long long)hp.split * S.slots[hp.problem].q_pad * k,
+                                  Q.d.n, hp.q0, hp.r0, hp.r1, Q.bin_pad / 4, 0});
+    }
+    std::vector<TopkFltWork> flt;
+    flt.reserve(S.flt.size());
+    for (const FltPiece& fp : S.flt) {
+        const SetRec &Q = c->sets[problems[fp.problem].query_set], &T = c->sets[problems[fp.problem].train_set];
+        const int dim = Q.fdim ? Q.fdim : kDim, dp = Q.fdim ? Q.fpad : kDim;
+        const bool vec = (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0;
+        flt.push_back(TopkFltWork{Q.d.f32, T.d.f32,
+                                  parts + Lo.part_off[fp.problem] + (long long)fp.split * S.slots[fp.problem].q_pad * k,
+                                  Q.d.n, fp.q0, fp.r0, fp.r1, dim, dp, T.d.n, vec ? 1 : 0});
+    }
+    if (!ham.empty()) HIPCHK(c, c->topk_ham_works.ensure(sizeof(TopkHamWork) * ham.size()));
+    if (!flt.empty()) HIPCHK(c, c->topk_flt_works.ensure(sizeof(TopkFltWork) * flt.size()));
+    // the device tables are rewritten in stream order (after the previous call's kernels)
+    const size_t pb = sizeof(TopkProb) * probs.size(), hb = sizeof(TopkHamWork) * ham.size(),
+                 fb = sizeof(TopkFltWork) * flt.size();
+    char* st = nullptr;
+    HIPCHK(c, c->stage.acquire(pb + hb + fb, &st));
+    memcpy(st, probs.data(), pb);
+    HIPCHK(c, hipMemcpyAsync(c->topk_probs.p, st, pb, hipMemcpyHostToDevice, c->stream));
+    if (hb) {
+        memcpy(st + pb, ham.data(), hb);
+        HIPCHK(c, hipMemcpyAsync(c->topk_ham_works.p, st + pb, hb, hipMemcpyHostToDevice, c->stream));
+    }
+    if (fb) {
+        memcpy(st + pb + hb, flt.data(), fb);
+        HIPCHK(c, hipMemcpyAsync(c->topk_flt_works.p, st + pb + hb, fb, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, c->stage.release_after(c->stream));
+    c->cur = c->stream;
+    ev_mark(c, "begin");
+    launch_knn_topk_hamming(c->topk_ham_works.as<TopkHamWork>(), (int)ham.size(), k, c->cur);
+    launch_knn_topk_float(c->topk_flt_works.as<TopkFltWork>(), (int)flt.size(), k, c->cur);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "knn");
+    launch_knn_topk_merge(c->topk_probs.as<TopkProb>(), n, max_nq, k, c->cur);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "ratio");
+    return MIM_OK;
+}
+
+mim_status mim_knn_batch_dev(mim_ctx* c, const mim_problem* problems, int32_t n, int32_t k, int32_t* idx_dev,
+                             float* dist_dev) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return knn_topk_locked(c, problems, n, k, idx_dev, dist_dev);
+}
+
+mim_status mim_knn_sets_dev(mim_ctx* c, int32_t query_set, int32_t train_set, int32_t k, int32_t* idx_dev,
+                            float* dist_dev) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const mim_problem pr{query_set, train_set};
+    return knn_topk_locked(c, &pr, 1, k, idx_dev, dist_dev);
+}
+
+// the host-buffer forms: private sets appended after the user's sets and removed afterwards (as
+// mim_knn2_hamming; no prep is flushed on this path, so their storage always goes back to the arena)
+static mim_status knn_topk_host(mim_ctx* c, int nq, int k, int32_t* idx, float* dist,
+                                const std::function<mim_status(bool, int32_t*)>& create) {
+    const size_t base = c->sets.size();
+    const Arena::Mark mark = c->arena.pos();
+    auto run = [&]() -> mim_status {
+        int32_t sq, st;
+        mim_status s = create(true, &sq);
+        if (s != MIM_OK) return s;
+        s = create(false, &st);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * k * nq));
+        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * k * nq));
+        const mim_problem pr{sq, st};
+        s = knn_topk_locked(c, &pr, 1, k, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>());
+        if (s != MIM_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * k * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * k * nq, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return MIM_OK;
+    };
+    const mim_status s = run();
+    ev_collect(c);
+    c->sets.resize(base);
+    c->arena.seek(mark);
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    return s;
+}
+
+mim_status mim_knn_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim, int32_t k,
+                      int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
+        return fail(c, MIM_EINVAL, "knn_l2: bad arguments");
+    if (dim < 1 || dim > kFltMaxDim) return fail(c, MIM_EINVAL, "knn_l2: dim must be 1..%d (got %d)", kFltMaxDim, dim);
+    if (k < 1 || k > MIM_KNN_MAX_K) return fail(c, MIM_EINVAL, "knn_l2: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
+    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
+    return knn_topk_host(c, nq, k, idx, dist, [&](bool query, int32_t* id) {
+        return set_create_f32_locked(c, query ? q : t, (int64_t)4 * dim, kp0.data(), query ? nq : nt, dim, 0, id);
+    });
+}
+
+mim_status mim_knn_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
+                           int32_t k, int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
+        return fail(c, MIM_EINVAL, "knn_hamming: bad arguments");
+    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "knn_hamming: width must be 1..64 bytes (got %d)", width);
+    if (k < 1 || k > MIM_KNN_MAX_K)
+        return fail(c, MIM_EINVAL, "knn_hamming: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
+    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
+    return knn_topk_host(c, nq, k, idx, dist, [&](bool query, int32_t* id) {
+        return set_create_bin_locked(c, query ? q : t, width, kp0.data(), query ? nq : nt, width, 0, id);
+    });
 }
 
 void mim_default_box_params(mim_box_params* p) {

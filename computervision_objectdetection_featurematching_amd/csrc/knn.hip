@@ -838,12 +838,14 @@ __global__ __launch_bounds__(256) void knn2_rescan_kernel(const ProbDev* __restr
         const int q = w.q0 + k + lane;
         const bool marked = q < nq && out[q].i2 == kRescan;
         unsigned long long m = __ballot(marked);
-        // waves take the marked queries round-robin
-        int pick = 0;
+        // a marked query belongs to the wave its position names.  (Not round-robin over the marks a wave
+        // sees: the waves read the marks at different times, and one that has already rewritten a record
+        // clears that mark for the waves behind it, which then counted differently and left a query to
+        // nobody.)
         while (m) {
             const int b = __builtin_ctzll(m);
             m &= m - 1;
-            if ((pick++ & 3) != wave) continue;
+            if ((b & 3) != wave) continue;
             const int qq = w.q0 + k + b;
             const float* qv = P->q.f32 + (size_t)qq * kDim;
             T2 t{FLT_MAX, INT_MAX, FLT_MAX, INT_MAX};

@@ -25,29 +25,18 @@
 #include <cfloat>
 #include <climits>
 
+#include "knn_float_arith.h"  // flt_round, flt_reduce, flt_tail4, flt_tile_rows; fp contraction off
 #include "mim_internal.h"
-
-#pragma clang fp contract(off)
 
 namespace mim {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 constexpr int kFltThreads = 256;       // 4 waves, a query per lane
 constexpr int kFltLdsFloats = 8192;    // 32 KiB train tile
 constexpr int kFltR = 4;               // train rows in flight on the streamed path
-// MIM_FLT_PACKED=0 (with -fno-slp-vectorize): the same arithmetic as scalar fp32 instructions, the build
-// that DESIGN.md §14 measures the packed one against
-#ifndef MIM_FLT_PACKED
-#define MIM_FLT_PACKED 1
-#endif
 static_assert(kFltThreads == kFltBlockQ, "one query per thread");
 static_assert(kFltRowPad * 128 <= kFltLdsFloats && 16 * kFltMaxDim <= kFltLdsFloats, "tile fits the LDS");
-
-// train rows per staged tile at a row stride of dp floats: divides kFltRowPad, a multiple of kFltR
-__device__ __forceinline__ int flt_tile_rows(int dp) { return dp <= 128 ? 64 : dp <= 256 ? 32 : 16; }
 
 struct FltTop {
     float k1, k2;      // the two smallest distances (sqrt values)
@@ -76,47 +65,6 @@ __device__ __forceinline__ void flt_insert(FltTop& s, float d2, int row) {
             }
         }
     }
-}
-
-// one round: 16 floats of the query (q[0..3]) against 16 of a train row (t[0..3], LDS, wave-uniform)
-// acc[2 v + h] holds lanes 2h, 2h + 1 of accumulator v
-__device__ __forceinline__ void flt_round(f2 (&acc)[8], const float4* q, const float4* t) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const float4 tv = t[v], qv = q[v];
-#if MIM_FLT_PACKED
-        const f2 d0 = f2{qv.x, qv.y} - f2{tv.x, tv.y};
-        const f2 d1 = f2{qv.z, qv.w} - f2{tv.z, tv.w};
-        acc[2 * v] = d0 * d0 + acc[2 * v];
-        acc[2 * v + 1] = d1 * d1 + acc[2 * v + 1];
-#else
-        const float e0 = qv.x - tv.x, e1 = qv.y - tv.y, e2 = qv.z - tv.z, e3 = qv.w - tv.w;
-        acc[2 * v].x = e0 * e0 + acc[2 * v].x;
-        acc[2 * v].y = e1 * e1 + acc[2 * v].y;
-        acc[2 * v + 1].x = e2 * e2 + acc[2 * v + 1].x;
-        acc[2 * v + 1].y = e3 * e3 + acc[2 * v + 1].y;
-#endif
-    }
-}
-
-__device__ __forceinline__ float flt_reduce(const f2 (&acc)[8]) {
-    const f2 s01 = ((acc[0] + acc[2]) + acc[4]) + acc[6];  // s0, s1
-    const f2 s23 = ((acc[1] + acc[3]) + acc[5]) + acc[7];  // s2, s3
-    const f2 t = s01 + s23;                                // s0 + s2, s1 + s3
-    return t.x + t.y;
-}
-
-// four tail elements, one by one
-__device__ __forceinline__ float flt_tail4(float d, const float4 qv, const float4 tv) {
-    float e = qv.x - tv.x;
-    d = d + e * e;
-    e = qv.y - tv.y;
-    d = d + e * e;
-    e = qv.z - tv.z;
-    d = d + e * e;
-    e = qv.w - tv.w;
-    d = d + e * e;
-    return d;
 }
 
 // whole tile [r, r + tile rows) of the train set into LDS: the set's storage has zero rows up to the

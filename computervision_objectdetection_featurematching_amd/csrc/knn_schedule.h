@@ -355,6 +355,28 @@ inline std::vector<KnnSchedProblem> knn_cross_problems(const std::vector<KnnSche
     return out;
 }
 
+// Top-k entries (mim_knn_batch_dev): where each problem's partial lists and output rows start,
+// in entries, after knn_hamming_plan / knn_float_plan set the slots' nsplit and q_pad.  A problem's partials
+// are [nsplit][q_pad][k] entries in a buffer of their own; its output rows start at k times the query rows
+// before it.
+struct KnnTopkLayout {
+    std::vector<long long> part_off, out_off;  // per problem
+    long long part = 0, out = 0;               // totals
+};
+inline KnnTopkLayout knn_topk_offsets(const std::vector<KnnSchedProblem>& in, const std::vector<KnnSchedSlot>& slots,
+                                      int k) {
+    KnnTopkLayout Lo;
+    Lo.part_off.resize(in.size());
+    Lo.out_off.resize(in.size());
+    for (size_t i = 0; i < in.size(); ++i) {
+        Lo.part_off[i] = Lo.part;
+        Lo.out_off[i] = Lo.out;
+        Lo.part += (long long)slots[i].nsplit * slots[i].q_pad * k;
+        Lo.out += (long long)std::max(in[i].nq, 0) * k;
+    }
+    return Lo;
+}
+
 // G: resident distance-kernel blocks of the device.
 inline KnnSchedule knn_schedule(const std::vector<KnnSchedProblem>& in, int G, int n_cu, int max_iters,
                                 const KnnSchedKnobs& knobs) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "knn_schedule.h"  // KnnWork, kKnnBlockQ and what it is derived from, the Hamming block constants
+#include "knn_topk_merge.h"  // TopkEnt
 
 namespace mim {
 
@@ -103,6 +104,48 @@ struct FltWork {
     int r0, r1;
     int dim;             // floats per row as the caller gave them (1..kFltMaxDim)
     int dp;              // floats per stored row: dim rounded up to a multiple of 4
+};
+
+// Top-k entries (knn_topk.hip): mim_knn_batch_dev and what is built on it.  The work items are
+// the pieces of knn_hamming_plan / knn_float_plan; a piece writes its queries' sorted lists of k entries to
+// the split's share of the top-k partials, [q_pad][k] TopkEnt.
+
+// Work item of the Hamming top-k kernel: as HamWork.
+struct TopkHamWork {
+    const uint32_t* q;   // padded query rows of the problem
+    const uint32_t* t;   // padded train rows
+    TopkEnt* out;        // the split's lists: the problem's partials + split * q_pad * k
+    int nq;
+    int q0;
+    int r0, r1;
+    int wdw;             // dwords per padded row: 4, 8 or 16
+    int pad_;
+};
+
+// Work item of the float top-k kernel: as FltWork, for generic float sets and for the f32 rows of 128-D
+// sets (dim = dp = 128), whose storage ends at row nt and whose pointers the caller may have borrowed us.
+struct TopkFltWork {
+    const float* q;
+    const float* t;
+    TopkEnt* out;
+    int nq;
+    int q0;
+    int r0, r1;
+    int dim;             // floats per row as the caller gave them (1..kFltMaxDim)
+    int dp;              // floats per stored row
+    int nt;              // train rows: no row from nt on is read
+    int vec;             // both row pointers are 16-byte aligned (dp is a multiple of 4): float4 loads
+};
+
+// One problem of the top-k merge and emit kernel.
+struct TopkProb {
+    const TopkEnt* parts;  // [nsplit][q_pad][k]
+    int32_t* idx;          // the problem's output rows [nq][k]
+    float* dist;
+    int nq;
+    int nsplit;
+    int q_pad;
+    int pad_;
 };
 
 // RANSAC state per problem (RANSACPointSetRegistrator::run locals, ptsetreg.cpp).

@@ -23,6 +23,7 @@ from . import _lib
 from ._lib import MimError, Params, Problem, RESULT_DTYPE
 
 DIM = 128
+KNN_MAX_K = 16  # MIM_KNN_MAX_K
 # cv::KeyPoint without class_id (mim_keypoint in include/mim.h)
 KEYPOINT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32),
                            ("response", np.float32), ("octave", np.int32)])
@@ -311,28 +312,44 @@ class Matcher:
         self._retire(int(n_keep))
 
     # ---- primitives -----------------------------------------------------------------------
-    def knn_match_arrays(self, query, train):
-        """knnMatch(query, train, k=2) as arrays: idx (nq,2) int32 (-1 absent), dist (nq,2) float32."""
+    @staticmethod
+    def _check_k(k) -> int:
+        if int(k) != k or not 1 <= k <= KNN_MAX_K:
+            raise ValueError(f"knnMatch: k must be an integer in 1..{KNN_MAX_K} (got {k!r})")
+        return int(k)
+
+    @staticmethod
+    def _dmatches(idx, dist):
+        """knnMatch's list of lists from (nq, k) arrays: absent entries (index -1) are dropped."""
+        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(idx.shape[1]) if idx[i, j] >= 0]
+                for i in range(idx.shape[0])]
+
+    def knn_match_arrays(self, query, train, k: int = 2):
+        """knnMatch(query, train, k) as arrays: idx (nq, k) int32 (-1 absent), dist (nq, k) float32.
+        k = 2 is the MFMA path of mim_knn2_l2; any other k in 1..16 is mim_knn_l2."""
+        k = self._check_k(k)
         q = np.ascontiguousarray(query, np.float32).reshape(-1, DIM)
         t = np.ascontiguousarray(train, np.float32).reshape(-1, DIM)
         nq = q.shape[0]
-        idx = np.full((max(nq, 1), 2), -1, np.int32)
-        dist = np.zeros((max(nq, 1), 2), np.float32)
-        self._check(self.L.mim_knn2_l2(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
-                                       t.shape[0], DIM, C.c_void_p(idx.ctypes.data), C.c_void_p(dist.ctypes.data)))
+        idx = np.full((max(nq, 1), k), -1, np.int32)
+        dist = np.zeros((max(nq, 1), k), np.float32)
+        if k == 2:
+            self._check(self.L.mim_knn2_l2(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                           t.shape[0], DIM, C.c_void_p(idx.ctypes.data), C.c_void_p(dist.ctypes.data)))
+        else:
+            self._check(self.L.mim_knn_l2(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                          t.shape[0], DIM, k, C.c_void_p(idx.ctypes.data),
+                                          C.c_void_p(dist.ctypes.data)))
         return idx[:nq], dist[:nq]
 
     def knn_match(self, query, train, k: int = 2):
-        """BFMatcher(NORM_L2).knnMatch(query, train, matches, k=2) -> list of lists of DMatch."""
-        if k != 2:
-            raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
-        idx, dist = self.knn_match_arrays(query, train)
-        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
-                for i in range(idx.shape[0])]
+        """BFMatcher(NORM_L2).knnMatch(query, train, matches, k), k in 1..16 -> list of lists of DMatch."""
+        return self._dmatches(*self.knn_match_arrays(query, train, k))
 
-    def knn_match_hamming_arrays(self, query, train):
-        """BFMatcher(NORM_HAMMING).knnMatch(query, train, k=2) on uint8 rows of one width (1..64 bytes),
-        as arrays: idx (nq, 2) int32 (-1 absent), dist (nq, 2) float32 (the integer distances)."""
+    def knn_match_hamming_arrays(self, query, train, k: int = 2):
+        """BFMatcher(NORM_HAMMING).knnMatch(query, train, k), k in 1..16, on uint8 rows of one width (1..64
+        bytes), as arrays: idx (nq, k) int32 (-1 absent), dist (nq, k) float32 (the integer distances)."""
+        k = self._check_k(k)
         q, t = np.asarray(query), np.asarray(train)
         if q.dtype != np.uint8 or t.dtype != np.uint8 or q.ndim != 2 or t.ndim != 2:
             raise ValueError("knn_match_hamming: uint8 (n, width) arrays are required")
@@ -340,24 +357,27 @@ class Matcher:
             raise ValueError(f"knn_match_hamming: query rows of {q.shape[1]} bytes, train rows of {t.shape[1]}")
         q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
         nq = q.shape[0]
-        idx = np.full((max(nq, 1), 2), -1, np.int32)
-        dist = np.zeros((max(nq, 1), 2), np.float32)
-        self._check(self.L.mim_knn2_hamming(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
-                                            t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
-                                            C.c_void_p(dist.ctypes.data)))
+        idx = np.full((max(nq, 1), k), -1, np.int32)
+        dist = np.zeros((max(nq, 1), k), np.float32)
+        if k == 2:
+            self._check(self.L.mim_knn2_hamming(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                                t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
+                                                C.c_void_p(dist.ctypes.data)))
+        else:
+            self._check(self.L.mim_knn_hamming(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                               t.shape[0], q.shape[1], k, C.c_void_p(idx.ctypes.data),
+                                               C.c_void_p(dist.ctypes.data)))
         return idx[:nq], dist[:nq]
 
     def knn_match_hamming(self, query, train, k: int = 2):
-        """BFMatcher(NORM_HAMMING).knnMatch(query, train, matches, k=2) -> list of lists of DMatch."""
-        if k != 2:
-            raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
-        idx, dist = self.knn_match_hamming_arrays(query, train)
-        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
-                for i in range(idx.shape[0])]
+        """BFMatcher(NORM_HAMMING).knnMatch(query, train, matches, k), k in 1..16 -> list of lists of DMatch."""
+        return self._dmatches(*self.knn_match_hamming_arrays(query, train, k))
 
-    def knn_match_float_arrays(self, query, train):
-        """BFMatcher(NORM_L2).knnMatch(query, train, k=2) on float32 rows of one dim 1..512 (mim_knn2_l2_f32),
-        as arrays: idx (nq, 2) int32 (-1 absent), dist (nq, 2) float32."""
+    def knn_match_float_arrays(self, query, train, k: int = 2):
+        """BFMatcher(NORM_L2).knnMatch(query, train, k), k in 1..16, on float32 rows of one dim 1..512
+        (mim_knn2_l2_f32 at k = 2, else mim_knn_l2), as arrays: idx (nq, k) int32 (-1 absent), dist (nq, k)
+        float32."""
+        k = self._check_k(k)
         q, t = np.asarray(query), np.asarray(train)
         if q.dtype != np.float32 or t.dtype != np.float32 or q.ndim != 2 or t.ndim != 2:
             raise ValueError("knn_match_float: float32 (n, dim) arrays are required")
@@ -365,20 +385,22 @@ class Matcher:
             raise ValueError(f"knn_match_float: query rows of dim {q.shape[1]}, train rows of dim {t.shape[1]}")
         q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
         nq = q.shape[0]
-        idx = np.full((max(nq, 1), 2), -1, np.int32)
-        dist = np.zeros((max(nq, 1), 2), np.float32)
-        self._check(self.L.mim_knn2_l2_f32(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
-                                           t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
-                                           C.c_void_p(dist.ctypes.data)))
+        idx = np.full((max(nq, 1), k), -1, np.int32)
+        dist = np.zeros((max(nq, 1), k), np.float32)
+        if k == 2:
+            self._check(self.L.mim_knn2_l2_f32(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                               t.shape[0], q.shape[1], C.c_void_p(idx.ctypes.data),
+                                               C.c_void_p(dist.ctypes.data)))
+        else:
+            self._check(self.L.mim_knn_l2(self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data),
+                                          t.shape[0], q.shape[1], k, C.c_void_p(idx.ctypes.data),
+                                          C.c_void_p(dist.ctypes.data)))
         return idx[:nq], dist[:nq]
 
     def knn_match_float(self, query, train, k: int = 2):
-        """BFMatcher(NORM_L2).knnMatch(query, train, matches, k=2) on float rows of any dim -> lists of DMatch."""
-        if k != 2:
-            raise ValueError("only k=2 is on the hot path (TestsDetector.cpp:60)")
-        idx, dist = self.knn_match_float_arrays(query, train)
-        return [[DMatch(i, int(idx[i, j]), 0, float(dist[i, j])) for j in range(2) if idx[i, j] >= 0]
-                for i in range(idx.shape[0])]
+        """BFMatcher(NORM_L2).knnMatch(query, train, matches, k), k in 1..16, on float rows of any dim -> lists of
+        DMatch."""
+        return self._dmatches(*self.knn_match_float_arrays(query, train, k))
 
     # ---- feature extraction either side of the matcher (ModelsDetector.cpp:75, TestsDetector.cpp:102,106)
     def sift_detect_compute(self, gray, mask=None, max_kp: int = 1 << 18):
@@ -631,9 +653,26 @@ class Matcher:
                                                 C.c_void_p(dist.ctypes.data)))
         return idx[:nq], dist[:nq]
 
-    def knn_sets_dev(self, qset: int, tset: int, idx_dev, dist_dev):
-        self._check(self.L.mim_knn2_sets_dev(self._ctx, qset, tset, C.c_void_p(_lib.ptr(idx_dev)),
-                                             C.c_void_p(_lib.ptr(dist_dev))))
+    def knn_sets_dev(self, qset: int, tset: int, idx_dev, dist_dev, k: int = 2):
+        """knnMatch rows of two registered sets into device buffers of k * nq entries, asynchronous: k = 2 is
+        mim_knn2_sets_dev, any other k in 1..16 mim_knn_sets_dev."""
+        k = self._check_k(k)
+        if k == 2:
+            self._check(self.L.mim_knn2_sets_dev(self._ctx, qset, tset, C.c_void_p(_lib.ptr(idx_dev)),
+                                                 C.c_void_p(_lib.ptr(dist_dev))))
+        else:
+            self._check(self.L.mim_knn_sets_dev(self._ctx, int(qset), int(tset), k, C.c_void_p(_lib.ptr(idx_dev)),
+                                                C.c_void_p(_lib.ptr(dist_dev))))
+
+    def knn_batch_dev(self, problems, k: int, idx_dev, dist_dev):
+        """mim_knn_batch_dev: the k nearest rows of every problem (query set, train set) of any mix of kinds in
+        one asynchronous call; problem i's rows start at entry k * (rows of the query sets before it) of the
+        device buffers.  Every k in 1..16 runs the top-k kernels here, k = 2 included."""
+        k = self._check_k(k)
+        arr = problems if isinstance(problems, np.ndarray) else np.asarray(list(problems), np.int32)
+        arr = np.ascontiguousarray(arr, np.int32).reshape(-1, 2)
+        self._check(self.L.mim_knn_batch_dev(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr), k,
+                                             C.c_void_p(_lib.ptr(idx_dev)), C.c_void_p(_lib.ptr(dist_dev))))
 
     def set_sampler_stream(self, on: bool):
         """Second-stream getSubset replay (mim_ctx_set_sampler_stream): on for a batch alone, off when

@@ -170,7 +170,7 @@ mim_status mim_set_rows(struct mim_ctx* ctx, int32_t set_id, int32_t cap, float*
 
 /* ---- primitive ops, host buffers, synchronous ------------------------------------------------
  * Each primitive call replaces the ctx's "last batch": after mim_knn2_l2 / _l2_f32 / _hamming / mim_ratio_filter /
- * mim_knn2_sets_dev there are no records (mim_batch_results returns none), after
+ * mim_knn2_sets_dev (and the mim_knn_* entries further down) there are no records (mim_batch_results returns none), after
  * mim_find_homography there is that call's one record. */
 /* ≙ BFMatcher(NORM_L2).knnMatch(q, t, matches, 2)            TestsDetector.cpp:36,60
  * idx[2i+k] = trainIdx of the k-th match of query i (-1 if absent), dist[2i+k] = DMatch::distance. */
@@ -263,6 +263,35 @@ mim_status mim_knn2_sets_dev(struct mim_ctx* ctx, int32_t query_set, int32_t tra
  * leaves the ctx without a batch (mim_batch_results returns no records). */
 mim_status mim_match_cross_sets(struct mim_ctx* ctx, int32_t query_set, int32_t train_set, int32_t* idx,
                                 float* dist);
+
+/* ---- knnMatch with any k from 1 to MIM_KNN_MAX_K (BFMatcher(norm).knnMatch(q, t, matches, k)) ----
+ * For every query row the k nearest train rows: the k smallest under (DMatch::distance as float32, train
+ * index), ascending, which is what OpenCV's insertion (`d < dist[K-1]`, then a shift while `dist[j] > d`)
+ * leaves.  Query i's entries are idx[k*i .. k*i+k) / dist[k*i .. k*i+k).  The distances carry the bits of the
+ * k = 2 entries of the kind: the popcount as float for binary rows, sqrtf of the squared distance in
+ * OpenCV's summation order for float rows; float rows are ranked on the sqrtf value (distinct squared
+ * distances can share one, and then the lower index comes first).  An entry is absent when the train set
+ * has fewer than k rows, or when the distance is not below FLT_MAX (an overflowed squared distance): index
+ * -1 and distance FLT_MAX.  k outside 1..MIM_KNN_MAX_K is MIM_EINVAL.  Like the other primitives these
+ * calls leave the ctx without a batch (mim_batch_results returns no records).  The k = 2 entries
+ * (mim_knn2_*) are unchanged and run their own kernels. */
+#define MIM_KNN_MAX_K 16
+/* n problems of registered sets, any mix of kinds in one call (128-D sets of mim_set_create with integer
+ * or non-integer rows, binary sets, generic float sets), with the pairing rules and errors of
+ * mim_batch_run: both sets of one kind, one width or dim, a train set below 2^18 rows.  Asynchronous on the
+ * ctx stream.  idx_dev / dist_dev: device buffers of k * (nq_0 + ... + nq_{n-1}) int32 / float32; problem
+ * i's rows start at entry k * (nq_0 + ... + nq_{i-1}). */
+mim_status mim_knn_batch_dev(struct mim_ctx* ctx, const mim_problem* problems, int32_t n, int32_t k,
+                             int32_t* idx_dev, float* dist_dev);
+/* The one-problem form: idx_dev / dist_dev hold k * nq entries. */
+mim_status mim_knn_sets_dev(struct mim_ctx* ctx, int32_t query_set, int32_t train_set, int32_t k,
+                            int32_t* idx_dev, float* dist_dev);
+/* Host buffers, synchronous: dense finite CV_32F rows of any dim 1..512 (idx / dist: k * nq entries). */
+mim_status mim_knn_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const float* t, int32_t nt,
+                      int32_t dim, int32_t k, int32_t* idx, float* dist);
+/* Host buffers, synchronous: dense CV_8U rows of `width` bytes, 1..64 (idx / dist: k * nq entries). */
+mim_status mim_knn_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
+                           int32_t width, int32_t k, int32_t* idx, float* dist);
 
 /* ---- feature extraction either side of the matcher ---------------------------
  * cv::KeyPoint without class_id; octave packed as OpenCV packs it (octave & 255 | layer << 8 |
@@ -436,7 +465,9 @@ mim_status mim_group_scene_points(mim_group* g, int32_t scene, float* out_xy, in
  * mode, 2 verdict mode; -1 before the first batch), whether or not timing is on.  Nor is "knn_cross": how
  * the last batch found the reverse nearest neighbours of a cross-check filter (0 not at all, 1 a second
  * sweep with the two sets swapped, 2 the one-pass Hamming kernel for every binary problem); the cross
- * compaction's time is under "ratio". */
+ * compaction's time is under "ratio".  Nor is "knn_topk_splits": the most train splits a problem of the last
+ * top-k call (mim_knn_batch_dev and what is built on it) was cut into; that call's distance kernels are
+ * timed under "knn" and its merge under "ratio". */
 double mim_last_kernel_ms(struct mim_ctx* ctx, const char* name);
 mim_status mim_set_timing(struct mim_ctx* ctx, int32_t enable);
 
