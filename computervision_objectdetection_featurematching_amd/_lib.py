@@ -20,7 +20,7 @@ EXPORTS = [
     "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",
     "mim_batch_results_dev", "mim_batch_results_copy", "mim_batch_problem_detail", "mim_batch_inlier_points", "mim_knn2_sets_dev", "mim_last_kernel_ms",
     "mim_set_timing", "mim_sift_detect_compute", "mim_sift_detect_compute_scales", "mim_sift_scales_sets",
-    "mim_resize_linear_u8", "mim_default_box_params", "mim_detect_boxes",
+    "mim_sift_debug_pyramid", "mim_resize_linear_u8", "mim_default_box_params", "mim_detect_boxes",
     "mim_group_shard", "mim_group_create", "mim_group_destroy", "mim_group_size", "mim_group_uses_rccl",
     "mim_group_ctx", "mim_group_last_error", "mim_group_set_create", "mim_group_scene_batch_run",
     "mim_group_results",
@@ -138,6 +138,7 @@ def load():
     L.mim_sift_detect_compute_scales.argtypes = [vp, u8p, i32, i32, C.c_int64, i32, vp, i32, vp, f32p, vp]
     L.mim_sift_scales_sets.argtypes = [vp, u8p, i32, i32, C.c_int64, i32, vp, vp, vp, i32, vp]
     L.mim_sift_scales_sets_image.argtypes = [vp, C.POINTER(Image), i32, vp, vp, vp, i32, vp]
+    L.mim_sift_debug_pyramid.argtypes = [vp, i32, vp, vp, vp, vp, C.c_int64, vp, vp]
     L.mim_cvt_bgr2gray_u8.argtypes = [vp, u8p, i32, i32, C.c_int64, u8p]
     L.mim_resize_linear_u8.argtypes = [vp, u8p, i32, i32, C.c_int64, u8p, i32, i32, C.c_double, C.c_double]
     L.mim_default_box_params.argtypes = [C.POINTER(BoxParams)]
@@ -167,7 +168,7 @@ def load():
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",
                  "mim_batch_problem_detail", "mim_batch_inlier_points", "mim_knn2_sets_dev", "mim_set_timing", "mim_ctx_set_sampler_stream",
                  "mim_sift_detect_compute", "mim_sift_detect_compute_scales", "mim_sift_scales_sets",
-                 "mim_resize_linear_u8", "mim_detect_boxes"):
+                 "mim_sift_debug_pyramid", "mim_resize_linear_u8", "mim_detect_boxes"):
         getattr(L, name).restype = C.c_int32
     _lib = L
     return L

@@ -254,6 +254,7 @@ struct mim_ctx {
     std::vector<hipEvent_t> ev_pool;  // recycled events (creating one per mark costs host time)
     std::map<std::string, double> last_ms;
     mim::SiftWs* sift = nullptr;
+    std::vector<mim::SiftWs*> sift_last;  // the workspaces of the last SIFT call's images (mim_sift_debug_pyramid)
     std::vector<mim::SiftWs*> sift_scales;  // mim_sift_detect_compute_scales: one per scale + the scene  // SIFT pyramid / candidate / descriptor workspace (first use)
 };
 
@@ -1389,8 +1390,10 @@ mim_status mim_sift_detect_compute(mim_ctx* c, const uint8_t* gray, int32_t rows
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->sift) c->sift = mim::sift_ws_create();
     int n = 0;
+    c->sift_last.clear();
     const int r = mim::sift_detect_compute(c->sift, c->stream, gray, rows, cols, step, mask, mask_step, max_kp, kps,
                                            desc, &n, c->err);
+    if (r == 0) c->sift_last.assign(1, c->sift);
     *n_kp = n;
     if (r == -1) return MIM_EDEVICE;
     if (r == -2) return MIM_ERANGE;
@@ -1410,13 +1413,35 @@ mim_status mim_sift_detect_compute_scales(mim_ctx* c, const uint8_t* gray, int32
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int> n(n_scales, 0);
+    c->sift_last.clear();
     const int r = mim::sift_detect_compute_scales(c->sift_scales, c->stream, gray, rows, cols, step, n_scales, scales,
                                                   max_kp, kps, desc, n.data(), c->err);
+    if (r == 0 || r == -2) c->sift_last.assign(c->sift_scales.begin(), c->sift_scales.begin() + n_scales);
     for (int i = 0; i < n_scales; ++i) n_kp[i] = n[i];
     if (r == -1) return MIM_EDEVICE;
     if (r == -2) return MIM_ERANGE;
     if (r == -3) return MIM_EINVAL;
     if (r == -4) return MIM_ELIMIT;
+    return MIM_OK;
+}
+
+mim_status mim_sift_debug_pyramid(mim_ctx* c, int32_t image_index, int32_t* n_oct, int32_t* orows, int32_t* ocols,
+                                  float* planes, int64_t cap, int64_t* need, int32_t* counters) {
+    if (!c) return MIM_EINVAL;
+    if (!n_oct || !orows || !ocols || !need || !counters || cap < 0)
+        return fail(c, MIM_EINVAL, "sift_debug_pyramid: bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->sift_last.empty()) return fail(c, MIM_EINVAL, "sift_debug_pyramid: no SIFT call completed on this ctx");
+    if (image_index < 0 || image_index >= (int32_t)c->sift_last.size())
+        return fail(c, MIM_EINVAL, "sift_debug_pyramid: image %d, the last SIFT call had %d", image_index,
+                    (int)c->sift_last.size());
+    HIPCHK(c, hipSetDevice(c->device));
+    long long nd = 0;
+    const int r = mim::sift_debug_pyramid(c->sift_last[image_index], c->stream, n_oct, orows, ocols, planes, cap, &nd,
+                                          counters, c->err);
+    *need = nd;
+    if (r == -1) return MIM_EDEVICE;
+    if (r == -3) return MIM_EINVAL;
     return MIM_OK;
 }
 
@@ -1472,8 +1497,10 @@ static mim_status sift_scales_sets_impl(mim_ctx* c, const uint8_t* img, int32_t 
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<mim::SiftDevOut> out(n_scales);
+    c->sift_last.clear();
     const int r = mim::sift_scales_device(c->sift_scales, c->stream, img, rows, cols, step, channels, n_scales, scales,
                                           out.data(), c->err);
+    if (r == 0) c->sift_last.assign(c->sift_scales.begin(), c->sift_scales.begin() + n_scales);
     if (r == -1) return MIM_EDEVICE;
     if (r == -3) return MIM_EINVAL;
     if (r == -4) return MIM_ELIMIT;

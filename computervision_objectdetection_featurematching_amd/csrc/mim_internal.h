@@ -288,4 +288,7 @@ int sift_bgr2gray_u8(SiftWs* w, hipStream_t st, const uint8_t* bgr, int rows, in
                      std::string& err);
 // out[j]'s n rows and keypoint positions into ddesc[j] / dkp[j], j < n <= 8, one launch (0, -1 HIP error)
 int sift_copy_sets(const SiftDevOut* out, int n, float* const* ddesc, float2* const* dkp, hipStream_t st);
+// test support: the pyramid and counters the last SIFT call left in w (mim_sift_debug_pyramid)
+int sift_debug_pyramid(SiftWs* w, hipStream_t st, int* n_oct, int* orows, int* ocols, float* planes, long long cap,
+                       long long* need, int* counters, std::string& err);
 }  // namespace mim

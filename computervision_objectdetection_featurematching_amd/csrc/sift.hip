@@ -1381,6 +1381,16 @@ struct SiftWs {
         size_t cap = 0;
         hipEvent_t ev = nullptr;  // recorded after the copy out of p
     } stage[2];
+    // test support (sift_debug_pyramid): the geometry sift_geometry computed for the image the last
+    // SIFT call put through this workspace and the counters sift_batch read back for it; valid only
+    // after a call that completed
+    struct Debug {
+        bool valid = false;
+        int n_oct = 0;
+        int orows[16] = {}, ocols[16] = {};
+        size_t goff[16] = {}, doff[16] = {};
+        int cnt[4] = {0, 0, 0, 0};  // candidates, raw keypoints, survivors, final keypoints
+    } dbg;
 };
 
 static hipError_t grow(void*& p, size_t& cap, size_t need) {
@@ -1540,6 +1550,7 @@ static int flatten(Flat& f, const std::vector<int>& imgs, F&& dims) {
 // Octave geometry, workspace buffers and the Pyr table of one image (host only)
 static int sift_geometry(SiftJob& J, std::string& err) {
     SiftWs* w = J.w;
+    w->dbg = SiftWs::Debug{};
     const int R = J.rows * 2, C = J.cols * 2;
     J.n_oct = (int)lrint(log((double)std::min(R, C)) / log(2.) - 2) + 1;
     if (J.n_oct < 1) {  // no octave (sides < 2 px after doubling): no keypoints, as OpenCV
@@ -1584,6 +1595,13 @@ static int sift_geometry(SiftJob& J, std::string& err) {
     J.d_kp2 = (mim_keypoint*)(J.d_surv + kCandCap);
     J.d_mask = J.mask ? (uint8_t*)(J.d_kp2 + kSortCap) : nullptr;
     SCHK(grow(w->desc, w->desc_cap, sizeof(float) * 128 * (size_t)kSortCap));
+    w->dbg.n_oct = J.n_oct;
+    for (int o = 0; o < J.n_oct; ++o) {
+        w->dbg.orows[o] = J.orows[o];
+        w->dbg.ocols[o] = J.ocols[o];
+        w->dbg.goff[o] = J.goff[o];
+        w->dbg.doff[o] = J.doff[o];
+    }
     return 0;
 }
 
@@ -1883,6 +1901,12 @@ static int sift_batch(std::vector<SiftJob>& jobs, SiftWs* bw, hipStream_t st, st
             J.n = J.h_cnt[3];
         }
     }
+    for (auto& J : jobs) {
+        SiftWs::Debug& D = J.w->dbg;
+        for (int q = 0; q < 3; ++q) D.cnt[q] = J.h_cnt[q];
+        D.cnt[3] = J.n;  // h_cnt[3] is negative where the host finished the image
+        D.valid = true;
+    }
     return 0;
 }
 
@@ -2083,6 +2107,48 @@ int sift_resize_u8(SiftWs* w, hipStream_t st, const uint8_t* src, int rows, int 
     resize_u8_kernel<<<nb, 256, 0, st>>>(A);
     SCHK(hipGetLastError());
     SCHK(hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, st));
+    SCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Test support: the pyramid the last SIFT call left in w (geometry and counters as recorded by
+// sift_geometry / sift_batch), copied out octave by octave: kNOL + 3 Gaussian planes, then kNOL + 2 DoG
+// planes.  *need = floats of all planes; planes null: sizes and counters only.  -3: no completed call
+// on w, or cap < *need.
+int sift_debug_pyramid(SiftWs* w, hipStream_t st, int* n_oct, int* orows, int* ocols, float* planes, long long cap,
+                       long long* need, int* counters, std::string& err) {
+    if (!w || !w->dbg.valid) {
+        err = "sift_debug_pyramid: no completed SIFT call for this image";
+        return -3;
+    }
+    const SiftWs::Debug& D = w->dbg;
+    long long total = 0;
+    for (int o = 0; o < 16; ++o) {
+        orows[o] = o < D.n_oct ? D.orows[o] : 0;
+        ocols[o] = o < D.n_oct ? D.ocols[o] : 0;
+        total += (long long)(2 * kNOL + 5) * orows[o] * ocols[o];
+    }
+    *n_oct = D.n_oct;
+    *need = total;
+    for (int q = 0; q < 4; ++q) counters[q] = D.cnt[q];
+    if (!planes) return 0;
+    if (cap < total) {
+        err = "sift_debug_pyramid: buffer of " + std::to_string(cap) + " floats, " + std::to_string(total) + " needed";
+        return -3;
+    }
+    if ((size_t)total * sizeof(float) > w->pyr_cap) {
+        err = "sift_debug_pyramid: recorded geometry exceeds the workspace";
+        return -3;
+    }
+    const float* P = (const float*)w->pyr;
+    float* dst = planes;
+    for (int o = 0; o < D.n_oct; ++o) {
+        const size_t plane = (size_t)D.orows[o] * D.ocols[o];
+        SCHK(hipMemcpyAsync(dst, P + D.goff[o], sizeof(float) * plane * (kNOL + 3), hipMemcpyDeviceToHost, st));
+        dst += plane * (kNOL + 3);
+        SCHK(hipMemcpyAsync(dst, P + D.doff[o], sizeof(float) * plane * (kNOL + 2), hipMemcpyDeviceToHost, st));
+        dst += plane * (kNOL + 2);
+    }
     SCHK(hipStreamSynchronize(st));
     return 0;
 }

@@ -448,6 +448,22 @@ class Matcher:
             o += int(c)
         return out
 
+    def sift_debug_pyramid(self, image_index: int = 0):
+        """Test support (mim_sift_debug_pyramid): the pyramid the last SIFT call on this matcher left in
+        its workspace for image `image_index` (0 after sift_detect_compute, the scale index after
+        sift_detect_compute_scales).  Returns (n_oct, orows[16], ocols[16], planes, counters): planes is
+        the flat float32 buffer, per octave 6 Gaussian then 5 DoG layers, each dense row-major;
+        counters = (candidates, raw keypoints, survivors, final keypoints)."""
+        n_oct, need = C.c_int32(), C.c_int64()
+        orows, ocols, cnt = np.zeros(16, np.int32), np.zeros(16, np.int32), np.zeros(4, np.int32)
+        args = (C.byref(n_oct), C.c_void_p(orows.ctypes.data), C.c_void_p(ocols.ctypes.data))
+        self._check(self.L.mim_sift_debug_pyramid(self._ctx, image_index, *args, None, 0, C.byref(need),
+                                                  C.c_void_p(cnt.ctypes.data)))
+        planes = np.zeros(max(need.value, 1), np.float32)
+        self._check(self.L.mim_sift_debug_pyramid(self._ctx, image_index, *args, C.c_void_p(planes.ctypes.data),
+                                                  need.value, C.byref(need), C.c_void_p(cnt.ctypes.data)))
+        return n_oct.value, orows, ocols, planes[:need.value], tuple(int(v) for v in cnt)
+
     def cvt_bgr2gray(self, bgr):
         """cv::cvtColor(bgr, gray, COLOR_BGR2GRAY) of an H x W x 3 uint8 image (preprocessImage,
         preprocessing.cpp:11) on the device: (R * 4899 + G * 9617 + B * 1868 + (1 << 13)) >> 14."""

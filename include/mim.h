@@ -333,6 +333,21 @@ mim_status mim_sift_scales_sets(struct mim_ctx* ctx, const uint8_t* gray, int32_
                                 int32_t n_scales, const float* scales, int32_t* set_ids, int32_t* n_kp, int32_t max_kp,
                                 mim_keypoint* kps);
 
+/* ---- test support --------------------------------------------------------------------------------
+ * The scale-space pyramid that the last SIFT call on this ctx left in its workspace for image
+ * image_index (always 0 after mim_sift_detect_compute; the scale index after
+ * mim_sift_detect_compute_scales / mim_sift_scales_sets*), read back as the product path computed it
+ * — nothing is recomputed.  *n_oct octaves of orows[o] x ocols[o] pixels (both arrays have 16 entries,
+ * the unused ones zeroed; an image with no octave gives *n_oct = 0).  planes (cap floats) receives,
+ * octave by octave, the 6 Gaussian layers and then the 5 DoG layers, each dense row-major; *need = the
+ * floats that takes, the sum over the octaves of 11 * rows * cols.  planes NULL: sizes and counters
+ * only.  counters[4] = the call's counts for that image: extremum candidates, raw keypoints (before
+ * sorting and duplicate removal), candidates that survived adjustLocalExtrema, final keypoints.
+ * MIM_EINVAL (text in mim_last_error) when no SIFT call has completed on this ctx, image_index is
+ * outside the last call's images, or cap < *need (*need is set).  Synchronous. */
+mim_status mim_sift_debug_pyramid(struct mim_ctx* ctx, int32_t image_index, int32_t* n_oct, int32_t* orows,
+                                  int32_t* ocols, float* planes, int64_t cap, int64_t* need, int32_t* counters);
+
 /* A host image as the reference holds its scenes (cv::Mat from imread, Output.cpp:33): rows x cols
  * pixels of `channels` bytes, channels = 1 (CV_8UC1) or 3 (CV_8UC3 in B, G, R order), row stride `step`
  * bytes >= cols * channels. */

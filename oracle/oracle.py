@@ -67,6 +67,8 @@ def lib():
         L.orc_resize_linear_u8.argtypes = [u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int, C.c_double, C.c_double]
         L.orc_sift_detect_compute.argtypes = [u8p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_sift_detect_compute.restype = C.c_int
+        L.orc_sift_pyramid.argtypes = [u8p, C.c_int, C.c_int, C.POINTER(C.c_int), i32p, i32p, C.c_void_p, C.c_int64]
+        L.orc_sift_pyramid.restype = C.c_int64
         L.orc_fast_atan2.argtypes = [C.c_float, C.c_float]
         L.orc_fast_atan2.restype = C.c_float
         _lib = L
@@ -229,6 +231,29 @@ def sift_detect_compute(gray: np.ndarray, mask: np.ndarray | None = None, max_kp
                                       max_kp, kps.ctypes.data, desc.ctypes.data)
     n = min(n, max_kp)
     return kps[:n].copy(), desc[:n].copy()
+
+
+def split_pyramid(n_oct: int, orows, ocols, planes: np.ndarray):
+    """Views into a flat pyramid buffer (sift_oracle.h layout): [(gauss (6, r, c), dog (5, r, c))] per octave."""
+    out, off = [], 0
+    for o in range(n_oct):
+        r, c = int(orows[o]), int(ocols[o])
+        g = planes[off:off + 6 * r * c].reshape(6, r, c)
+        d = planes[off + 6 * r * c:off + 11 * r * c].reshape(5, r, c)
+        out.append((g, d))
+        off += 11 * r * c
+    return out
+
+
+def sift_pyramid(gray: np.ndarray):
+    """The pyramid sift_detect_compute builds for gray: (n_oct, orows[16], ocols[16], flat float32 planes)."""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    n_oct = C.c_int(0)
+    orows, ocols = np.zeros(16, np.int32), np.zeros(16, np.int32)
+    need = lib().orc_sift_pyramid(gray, gray.shape[0], gray.shape[1], C.byref(n_oct), orows, ocols, None, 0)
+    planes = np.zeros(max(need, 1), np.float32)
+    lib().orc_sift_pyramid(gray, gray.shape[0], gray.shape[1], C.byref(n_oct), orows, ocols, planes.ctypes.data, need)
+    return n_oct.value, orows, ocols, planes[:need]
 
 
 def fast_atan2(y: float, x: float) -> float:

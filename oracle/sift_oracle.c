@@ -387,8 +387,14 @@ static int kp_cmp(const void* a_, const void* b_) {
     return 0;
 }
 
-int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_t* mask, int max_kp,
-                            orc_keypoint* kps, float* desc) {
+/* createInitialImage, buildGaussianPyramid and buildDoGPyramid: n_oct octaves of NOL + 3 Gaussian
+ * layers (gp[o * (NOL + 3) + i]) and NOL + 2 DoG layers (dog[o * (NOL + 2) + i]) */
+typedef struct {
+    int n_oct;
+    img_t *gp, *dog;
+} pyramid_t;
+
+static pyramid_t build_pyramid(const uint8_t* img, int rows, int cols) {
     /* createInitialImage: float, x2 INTER_LINEAR, blur sqrt(sigma^2 - (2 * 0.5)^2) */
     img_t g = img_new(rows, cols);
     for (int i = 0; i < rows * cols; ++i) g.d[i] = (float)img[i];
@@ -408,6 +414,7 @@ int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_
         const double sig_prev = pow(k, (double)(i - 1)) * 1.6, sig_total = sig_prev * k;
         sig[i] = sqrt(sig_total * sig_total - sig_prev * sig_prev);
     }
+    if (n_oct <= 0) free(base.d);  /* no octave takes it over */
     img_t* gp = (img_t*)calloc((size_t)n_oct * (NOL + 3), sizeof(img_t));
     for (int o = 0; o < n_oct; o++)
         for (int i = 0; i < NOL + 3; i++) {
@@ -431,6 +438,46 @@ int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_
             for (int p = 0; p < a.rows * a.cols; ++p) d.d[p] = b.d[p] - a.d[p];
             dog[o * (NOL + 2) + i] = d;
         }
+    pyramid_t P = {n_oct, gp, dog};
+    return P;
+}
+
+static void free_pyramid(pyramid_t P) {
+    for (int i = 0; i < P.n_oct * (NOL + 3); ++i) free(P.gp[i].d);
+    for (int i = 0; i < P.n_oct * (NOL + 2); ++i) free(P.dog[i].d);
+    free(P.gp);
+    free(P.dog);
+}
+
+int64_t orc_sift_pyramid(const uint8_t* img, int rows, int cols, int* n_oct, int* orows, int* ocols, float* planes,
+                         int64_t cap) {
+    const pyramid_t P = build_pyramid(img, rows, cols);
+    int64_t need = 0;
+    for (int o = 0; o < ORC_SIFT_MAX_OCT; ++o) orows[o] = ocols[o] = 0;
+    for (int o = 0; o < P.n_oct && o < ORC_SIFT_MAX_OCT; ++o) {
+        const img_t b = P.gp[o * (NOL + 3)];
+        orows[o] = b.rows;
+        ocols[o] = b.cols;
+        need += (int64_t)(2 * NOL + 5) * b.rows * b.cols;
+    }
+    *n_oct = P.n_oct > 0 ? P.n_oct : 0;
+    if (planes && need <= cap && P.n_oct <= ORC_SIFT_MAX_OCT) {
+        float* w = planes;
+        for (int o = 0; o < P.n_oct; ++o) {
+            const size_t px = (size_t)orows[o] * ocols[o];
+            for (int i = 0; i < NOL + 3; ++i, w += px) memcpy(w, P.gp[o * (NOL + 3) + i].d, px * sizeof(float));
+            for (int i = 0; i < NOL + 2; ++i, w += px) memcpy(w, P.dog[o * (NOL + 2) + i].d, px * sizeof(float));
+        }
+    }
+    free_pyramid(P);
+    return need;
+}
+
+int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_t* mask, int max_kp,
+                            orc_keypoint* kps, float* desc) {
+    const pyramid_t P = build_pyramid(img, rows, cols);
+    const int n_oct = P.n_oct;
+    img_t *const gp = P.gp, *const dog = P.dog;
     /* findScaleSpaceExtrema */
     const int threshold = cv_floor(0.5 * 0.04 / NOL * 255);  /* contrastThreshold: double member */
     kplist kl = {0, 0, 0};
@@ -518,9 +565,6 @@ int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_
     }
     const int n = kl.n;
     free(kl.v);
-    for (int i = 0; i < n_oct * (NOL + 3); ++i) free(gp[i].d);
-    for (int i = 0; i < n_oct * (NOL + 2); ++i) free(dog[i].d);
-    free(gp);
-    free(dog);
+    free_pyramid(P);
     return n;
 }

@@ -39,6 +39,15 @@ void orc_resize_linear_u8(const uint8_t* src, int rows, int cols, uint8_t* dst, 
 int orc_sift_detect_compute(const uint8_t* img, int rows, int cols, const uint8_t* mask, int max_kp,
                             orc_keypoint* kps, float* desc);
 
+/* The scale-space pyramid that orc_sift_detect_compute builds for img (the same function builds both):
+ * *n_oct octaves, octave o of orows[o] x ocols[o] pixels (both arrays have ORC_SIFT_MAX_OCT entries,
+ * the unused ones zeroed).  planes receives, octave by octave, the 6 Gaussian layers and then the 5
+ * DoG layers, each dense row-major float32.  Returns the number of floats needed, the sum over the
+ * octaves of 11 * rows * cols; planes is written only if it is non-null and cap (in floats) suffices. */
+#define ORC_SIFT_MAX_OCT 16
+int64_t orc_sift_pyramid(const uint8_t* img, int rows, int cols, int* n_oct, int* orows, int* ocols, float* planes,
+                         int64_t cap);
+
 /* OpenCV's fastAtan2 (degrees, polynomial approximation), for the KAT tests. */
 float orc_fast_atan2(float y, float x);
 

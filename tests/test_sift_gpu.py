@@ -144,6 +144,16 @@ def test_sift_synthetic(matcher, oracle, seed, shape):
     assert len(ok) > 10
 
 
+@pytest.mark.parametrize("seed,shape", [(1, (96, 128)), (2, (200, 300)), (3, (61, 97)), (4, (256, 256))])
+def test_sift_synthetic_multi(matcher, oracle, seed, shape):
+    """The shapes of test_sift_synthetic on noise at six scales (sift_inputs.multi): ten times the
+    keypoints of blobs(), in every octave."""
+    from sift_inputs import multi
+    img = multi(seed, *shape)
+    gk, gd, ok = run_both(matcher, oracle, img, label=f"multi{seed}{shape}")
+    assert len(ok) > 60
+
+
 def test_sift_descriptor_contract(matcher):
     """CV_32F rows of integers in [0, 255] (the i8 distance path's precondition, mim.h)."""
     k, d = matcher.sift_detect_compute(blobs(7, 160, 200))

@@ -93,3 +93,48 @@ def test_sift_rotation_90(oracle):
     assert np.hypot(k1["x"][j] - px, k1["y"][j] - py) < 0.5
     da = (k1["angle"][j] - k0["angle"][i]) % 360
     assert min(abs(da - 90), abs(da - 270)) < 5 or min(da, 360 - da) < 5 or abs(da - 180) < 5
+
+
+def test_oracle_output_unchanged_by_pyramid_split(oracle):
+    """orc_sift_detect_compute and orc_sift_pyramid share one pyramid builder; the keypoints and
+    descriptors still equal, byte for byte, what the oracle gave before the builder was split out
+    (tests/golden/sift_oracle_digests.json, written by make_sift_oracle_digests.py)."""
+    import json
+    import os
+    from golden.make_sift_oracle_digests import digest, inputs
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sift_oracle_digests.json")
+    with open(path) as f:
+        want = json.load(f)
+    seen = []
+    for label, img, mask in inputs():
+        assert digest(oracle, img, mask) == want[label], label
+        seen.append(label)
+    assert sorted(seen) == sorted(want) and len(seen) == 27
+
+
+def test_pyramid_self_consistency(oracle):
+    """orc_sift_pyramid: octave 0 is the doubled image's size, every later octave's layer 0 is every
+    second pixel of the previous octave's layer 3, DoG i = layer i + 1 - layer i exactly, and the
+    octave count is OpenCV's cvRound(log2(min side of octave 0) - 2) + 1."""
+    from sift_inputs import PYRAMID_SHAPES, multi, pyramid_case
+    cases = [pyramid_case(i) for i in range(len(PYRAMID_SHAPES))] + [multi(5, 70, 52)]
+    for img in cases:
+        rows, cols = img.shape
+        n_oct, orows, ocols, planes = oracle.sift_pyramid(img)
+        assert (orows[0], ocols[0]) == (2 * rows, 2 * cols)
+        assert n_oct == int(np.rint(np.log2(2 * min(rows, cols)) - 2)) + 1
+        assert np.all(orows[n_oct:] == 0) and np.all(ocols[n_oct:] == 0)
+        assert planes.size == sum(11 * int(orows[o]) * int(ocols[o]) for o in range(n_oct))
+        pyr = oracle.split_pyramid(n_oct, orows, ocols, planes)
+        for o, (g, d) in enumerate(pyr):
+            assert np.all(np.isfinite(g))
+            for i in range(5):
+                assert np.array_equal(d[i], g[i + 1] - g[i]), (img.shape, o, i)
+            if o > 0:
+                assert (orows[o], ocols[o]) == (orows[o - 1] // 2, ocols[o - 1] // 2)
+                prev = pyr[o - 1][0][3]
+                assert np.array_equal(g[0], prev[::2, ::2][:orows[o], :ocols[o]]), (img.shape, o)
+        # a blur is a weighted mean with weights summing to 1 (to float rounding): the range is kept
+        assert all(-1e-3 <= g.min() and g.max() <= 255 + 1e-3 for g, _ in pyr)
+    n_oct, orows, ocols, planes = oracle.sift_pyramid(np.full((1, 2), 50, np.uint8))  # no octave
+    assert n_oct == 0 and planes.size == 0 and not orows.any() and not ocols.any()
