@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libmim.so")
-SOURCES = ["knn.hip", "hamming.hip", "knn_float.hip", "knn_topk.hip", "ransac.hip", "sift.hip", "api.cpp", "group.cpp"]
+SOURCES = ["knn.hip", "hamming.hip", "knn_float.hip", "knn_topk.hip", "radius.hip", "ransac.hip", "sift.hip", "api.cpp", "group.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the RANSAC/DLT arithmetic must not be FMA-contracted (OpenCV's calib3d
 # x86-64 build has no FMA), see DESIGN.md "Floating-point contract".
@@ -36,7 +36,8 @@ def needs_build() -> bool:
     t = os.path.getmtime(SO)
     deps = sources() + [os.path.join(CSRC, "mim_internal.h"), os.path.join(CSRC, "knn_schedule.h"),
                         os.path.join(CSRC, "mim_debug.h"), os.path.join(CSRC, "knn_float_arith.h"),
-                        os.path.join(CSRC, "knn_topk_merge.h"), os.path.join(HERE, "..", "include", "mim.h")]
+                        os.path.join(CSRC, "knn_topk_merge.h"), os.path.join(CSRC, "radius.h"),
+                        os.path.join(CSRC, "radius_host.h"), os.path.join(HERE, "..", "include", "mim.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

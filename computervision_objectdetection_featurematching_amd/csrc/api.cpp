@@ -23,6 +23,7 @@
 #include "../../include/mim.h"
 #include "../../include/mim_detect.hpp"
 #include "mim_internal.h"
+#include "radius.h"
 
 namespace mim {
 void launch_prep_batch(const PrepJob* jobs, int njobs, int total_tiles, hipStream_t st);
@@ -201,6 +202,19 @@ struct mim_ctx {
     // top-k entries (mim_knn_batch_dev): partial lists, work items and the merge's problem table
     DevBuf topk_parts, topk_ham_works, topk_flt_works, topk_probs;
     int topk_splits = 0;  // the most train splits of a problem of the last such call
+    // radius matching (mim_radius_count / mim_radius_fill_dev): the call's arrays, the work items
+    // of its three distance kernels, and what the last count call left for the fills that follow it
+    DevBuf rad_counts, rad_cursor, rad_offsets, rad_meta, rad_keys, rad_scratch, rad_ham_works, rad_flt_works, rad_i8_works,
+        rad_probs;
+    struct RadLast {
+        bool valid = false;
+        std::vector<mim_problem> problems;
+        float r = 0.f;
+        long long gen = -1;              // sets generation at the count
+        long long n_queries = 0, total = 0, longest = 0;
+        int n_ham = 0, n_flt = 0, n_i8_works = 0, n_i8_blocks = 0;
+        bool filled = false;             // a fill has used the cursors since the scan cleared them
+    } rad;
     int knn_cross = 0;       // how the last batch found the reverse neighbours: 0 not, 1 second sweep, 2 fused
     int last_filter = 0;     // the last mim_batch_run_filter's filter, for its re-run
     int n_cu = 0;         // compute units of the device (first batch)
@@ -335,7 +349,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->rad_counts, &c->rad_cursor, &c->rad_offsets, &c->rad_meta, &c->rad_keys, &c->rad_scratch, &c->rad_ham_works, &c->rad_flt_works, &c->rad_i8_works, &c->rad_probs, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -377,6 +391,7 @@ double mim_last_kernel_ms(mim_ctx* c, const char* name) {
     if (!c || !name) return -1;
     if (!strcmp(name, "knn_cross")) return c->knn_cross;  // nor this: how the last batch found the reverse neighbours
     if (!strcmp(name, "knn_topk_splits")) return c->topk_splits;  // nor this: the last top-k call's most train splits
+    if (!strcmp(name, "radius_sort_cap")) return kRadSortCap;  // nor this: the longest list the radius sort keeps in LDS
     if (!strcmp(name, "knn_mode")) return c->knn_mode;  // not a time: the form the last batch's distance kernel ran in
     auto it = c->last_ms.find(name);
     return it == c->last_ms.end() ? -1 : it->second;
@@ -1341,6 +1356,292 @@ mim_status mim_knn_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
     return knn_topk_host(c, nq, k, idx, dist, [&](bool query, int32_t* id) {
+        return set_create_bin_locked(c, query ? q : t, width, kp0.data(), query ? nq : nt, width, 0, id);
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Radius matching: count + scan, then fill + sort + emit of the last count.
+// ---------------------------------------------------------------------------------------------
+static RadArgs radius_args(mim_ctx* c) {
+    RadArgs a{};
+    a.counts = c->rad_counts.as<int>();
+    a.cursor = c->rad_cursor.as<int>();
+    a.offsets = c->rad_offsets.as<long long>();
+    a.keys = c->rad_keys.as<unsigned long long>();
+    a.flt_t = radius_flt_threshold(c->rad.r);
+    a.ham_t = radius_ham_threshold(c->rad.r);
+    a.int_t2 = radius_int_threshold(c->rad.r);
+    return a;
+}
+
+// one pass of the three distance kernels over the work items the last count left on the device
+static void radius_launch(mim_ctx* c, const RadArgs& a, bool fill) {
+    const KnnWork* w = c->rad_i8_works.as<KnnWork>();
+    launch_radius_hamming(c->rad_ham_works.as<RadHamWork>(), c->rad.n_ham, a, fill, c->cur);
+    launch_radius_float(c->rad_flt_works.as<RadFltWork>(), c->rad.n_flt, a, fill, c->cur);
+    if (c->rad.n_i8_works > 0)
+        launch_radius_i8(c->rad_probs.as<RadI8Prob>(), w, reinterpret_cast<const int*>(w + c->rad.n_i8_works),
+                         c->rad.n_i8_blocks, a, fill, c->cur);
+}
+
+// With the lock held.  The work lists are those of knn_hamming_plan / knn_float_plan (128-D sets at dim 128, as
+// the top-k entries) and, for the 128-D sets again, the i8 units of knn_schedule_static: a 128-D problem is in
+// both lists, and the sets' integrality flags decide on the device which kernel's blocks do its pairs.
+static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, int n, float r, int64_t* offsets_dev,
+                                      int64_t* total) {
+    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
+    c->last_gen = -1;
+    c->last_fh = false;
+    c->rad.valid = false;
+    if (!total || n < 0 || (n > 0 && !problems)) return fail(c, MIM_EINVAL, "radius: bad arguments");
+    *total = 0;
+    if (!radius_arg_ok(r))
+        return fail(c, MIM_EINVAL, "radius: max_distance must be above FLT_EPSILON (got %g)", (double)r);
+    mim_status s = flush_preps(c);  // the 128-D sets' fragment tiles, norm blocks and flags
+    if (s != MIM_OK) return s;
+    s = device_limits(c);
+    if (s != MIM_OK) return s;
+    std::vector<KnnSchedProblem> in(n), in8(n);
+    std::vector<long long> qoff(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const int qs = problems[i].query_set, ts = problems[i].train_set;
+        s = check_problem_sets(c, i, qs, ts, false);
+        if (s != MIM_OK) return s;
+        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
+        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
+        in[i].fdim = Q.bin_pad ? 0 : Q.fdim ? Q.fdim : kDim;
+        in8[i] = in[i];
+        const bool sift = !Q.bin_pad && !Q.fdim;
+        in8[i].bin = !sift;  // out of the i8 schedule
+        in8[i].fdim = 0;
+        qoff[i + 1] = qoff[i] + Q.d.n;
+    }
+    const long long nqs = qoff[n];
+    KnnSchedule S, S8;
+    S.slots.assign(n, KnnSchedSlot{});
+    S8.slots.assign(n, KnnSchedSlot{});
+    knn_hamming_plan(in, c->n_cu, S);
+    knn_float_plan(in, c->n_cu, S);
+    knn_schedule_static(in8, c->knn_grid, -1, S8);
+    std::vector<RadHamWork> ham;
+    ham.reserve(S.ham.size());
+    for (const HamPiece& hp : S.ham) {
+        const SetRec &Q = c->sets[problems[hp.problem].query_set], &T = c->sets[problems[hp.problem].train_set];
+        ham.push_back(RadHamWork{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag),
+                                 qoff[hp.problem], Q.d.n, hp.q0, hp.r0, hp.r1, Q.bin_pad / 4, 0});
+    }
+    std::vector<RadFltWork> flt;
+    flt.reserve(S.flt.size());
+    for (const FltPiece& fp : S.flt) {
+        const SetRec &Q = c->sets[problems[fp.problem].query_set], &T = c->sets[problems[fp.problem].train_set];
+        const int dim = Q.fdim ? Q.fdim : kDim, dp = Q.fdim ? Q.fpad : kDim;
+        const bool vec = (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0;
+        flt.push_back(RadFltWork{Q.d.f32, T.d.f32, Q.fdim ? nullptr : Q.d.flags, Q.fdim ? nullptr : T.d.flags,
+                                 qoff[fp.problem], Q.d.n, fp.q0, fp.r0, fp.r1, dim, dp, T.d.n, vec ? 1 : 0});
+    }
+    std::vector<RadI8Prob> probs(n);
+    for (int i = 0; i < n; ++i)
+        probs[i] = RadI8Prob{c->sets[problems[i].query_set].d, c->sets[problems[i].train_set].d, qoff[i]};
+    const size_t wb = sizeof(KnnWork) * S8.works.size(), sb = sizeof(int) * S8.seg.size();
+    HIPCHK(c, c->rad_counts.ensure(sizeof(int) * (nqs + 1)));
+    HIPCHK(c, c->rad_cursor.ensure(sizeof(int) * (nqs + 1)));
+    HIPCHK(c, c->rad_offsets.ensure(sizeof(long long) * (nqs + 1)));
+    HIPCHK(c, c->rad_meta.ensure(sizeof(long long) * (2 + 2 * (size_t)radius_scan_blocks(nqs))));
+    HIPCHK(c, c->rad_probs.ensure(sizeof(RadI8Prob) * std::max(n, 1)));
+    if (!ham.empty()) HIPCHK(c, c->rad_ham_works.ensure(sizeof(RadHamWork) * ham.size()));
+    if (!flt.empty()) HIPCHK(c, c->rad_flt_works.ensure(sizeof(RadFltWork) * flt.size()));
+    if (wb) HIPCHK(c, c->rad_i8_works.ensure(wb + sb));
+    // the device tables are rewritten in stream order (after the previous call's kernels)
+    const size_t pb = sizeof(RadI8Prob) * probs.size(), hb = sizeof(RadHamWork) * ham.size(),
+                 fb = sizeof(RadFltWork) * flt.size();
+    char* st = nullptr;
+    HIPCHK(c, c->stage.acquire(pb + hb + fb + wb + sb + 16, &st));
+    size_t o = 0;
+    auto put = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        if (!bytes) return hipSuccess;
+        memcpy(st + o, src, bytes);
+        const hipError_t e = hipMemcpyAsync(dst, st + o, bytes, hipMemcpyHostToDevice, c->stream);
+        o += bytes;
+        return e;
+    };
+    HIPCHK(c, put(c->rad_probs.p, probs.data(), pb));
+    HIPCHK(c, put(c->rad_ham_works.p, ham.data(), hb));
+    HIPCHK(c, put(c->rad_flt_works.p, flt.data(), fb));
+    if (wb) {
+        HIPCHK(c, put(c->rad_i8_works.p, S8.works.data(), wb));
+        HIPCHK(c, put(static_cast<char*>(c->rad_i8_works.p) + wb, S8.seg.data(), sb));
+    }
+    HIPCHK(c, c->stage.release_after(c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rad_counts.p, 0, sizeof(int) * (nqs + 1), c->stream));
+    c->rad.problems.assign(problems, problems + n);
+    c->rad.r = r;
+    c->rad.gen = c->sets_gen;
+    c->rad.n_queries = nqs;
+    c->rad.n_ham = (int)ham.size();
+    c->rad.n_flt = (int)flt.size();
+    c->rad.n_i8_works = (int)S8.works.size();
+    c->rad.n_i8_blocks = S8.works.empty() ? 0 : S8.n_blocks;
+    c->cur = c->stream;
+    ev_mark(c, "begin");
+    radius_launch(c, radius_args(c), false);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "radius_count");
+    launch_radius_scan(c->rad_counts.as<int>(), c->rad_cursor.as<int>(), c->rad_offsets.as<long long>(),
+                       reinterpret_cast<long long*>(offsets_dev), nqs, c->rad_meta.as<long long>(), c->cur);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "radius_scan");
+    long long meta[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(meta, c->rad_meta.p, sizeof meta, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the one scalar the caller sizes its buffers by
+    ev_collect(c);
+    c->rad.total = meta[0];
+    c->rad.longest = meta[1];
+    c->rad.filled = false;
+    c->rad.valid = true;
+    *total = meta[0];
+    return MIM_OK;
+}
+
+static mim_status radius_fill_locked(mim_ctx* c, int32_t* idx_dev, float* dist_dev, int64_t cap) {
+    c->last_n = 0;
+    c->last_gen = -1;
+    c->last_fh = false;
+    if (!c->rad.valid) return fail(c, MIM_EINVAL, "radius_fill: no mim_radius_count call to fill");
+    if (c->rad.gen != c->sets_gen)
+        return fail(c, MIM_EINVAL, "radius_fill: sets were cleared or truncated since the mim_radius_count call");
+    if (cap < c->rad.total)
+        return fail(c, MIM_ERANGE, "radius_fill: %lld matches, room for %lld", c->rad.total, (long long)cap);
+    if (c->rad.total == 0) return MIM_OK;
+    if (!idx_dev || !dist_dev) return fail(c, MIM_EINVAL, "radius_fill: null output");
+    if (c->rad_keys.ensure(sizeof(unsigned long long) * c->rad.total) != hipSuccess)
+        return fail(c, MIM_ENOMEM, "radius_fill: key buffer of %lld entries", c->rad.total);
+    if (c->rad.longest > kRadSortCap && c->rad_scratch.ensure(sizeof(unsigned long long) * c->rad.total) != hipSuccess)
+        return fail(c, MIM_ENOMEM, "radius_fill: merge buffer of %lld entries", c->rad.total);
+    c->cur = c->stream;
+    if (c->rad.filled) HIPCHK(c, hipMemsetAsync(c->rad_cursor.p, 0, sizeof(int) * c->rad.n_queries, c->stream));
+    c->rad.filled = true;
+    ev_mark(c, "begin");
+    radius_launch(c, radius_args(c), true);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "radius_fill");
+    launch_radius_sort(c->rad_offsets.as<long long>(), c->rad.n_queries, c->rad_keys.as<unsigned long long>(),
+                       c->rad_scratch.as<unsigned long long>(), idx_dev, dist_dev, c->cur);
+    HIPCHK(c, hipGetLastError());
+    ev_mark(c, "radius_sort");
+    return MIM_OK;
+}
+
+// the host-buffer forms: private sets appended after the user's sets and removed afterwards.  The 128-D form
+// flushes its sets' prep, whose flags block comes from the arena after their storage: everything goes back
+// unless sets of the user's were still waiting for their prep and share that block (as mim_knn2_hamming).
+static mim_status radius_host(mim_ctx* c, int nq, float r, int64_t* offsets, int32_t* idx, float* dist, int64_t cap,
+                              const std::function<mim_status(bool, int32_t*)>& create) {
+    const size_t base = c->sets.size();
+    const Arena::Mark mark = c->arena.pos();
+    const bool reclaim = c->pend.empty();
+    auto run = [&]() -> mim_status {
+        int32_t sq, st;
+        mim_status s = create(true, &sq);
+        if (s != MIM_OK) return s;
+        s = create(false, &st);
+        if (s != MIM_OK) return s;
+        const mim_problem pr{sq, st};
+        int64_t total = 0;
+        s = radius_count_locked(c, &pr, 1, r, nullptr, &total);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(offsets, c->rad_offsets.p, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!idx) return MIM_OK;  // offsets only
+        if (total > cap) return fail(c, MIM_ERANGE, "radius: %lld matches, room for %lld", (long long)total, (long long)cap);
+        if (total == 0) return MIM_OK;
+        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * total));
+        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * total));
+        s = radius_fill_locked(c, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>(), total);
+        if (s != MIM_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return MIM_OK;
+    };
+    const mim_status s = run();
+    ev_collect(c);
+    // the private sets go, with their pending preps (a failure before the flush) and the flush that covered them alone
+    size_t m = 0;
+    for (size_t j = 0; j < c->pend.size(); ++j)
+        if (c->pend_set[j] < (int)base) {
+            c->pend[m] = c->pend[j];
+            c->pend_set[m++] = c->pend_set[j];
+        }
+    c->pend.resize(m);
+    c->pend_set.resize(m);
+    c->flushes.erase(std::remove_if(c->flushes.begin(), c->flushes.end(),
+                                    [base](const std::pair<int, Arena::Mark>& f) { return f.first >= (int)base; }),
+                     c->flushes.end());
+    c->sets.resize(base);
+    if (reclaim) c->arena.seek(mark);
+    c->rad.valid = false;  // its sets are gone
+    c->last_n = 0;
+    c->last_gen = -1;
+    c->last_fh = false;
+    return s;
+}
+
+extern "C" {
+
+mim_status mim_radius_count(mim_ctx* c, const mim_problem* problems, int32_t n, float max_distance,
+                            int64_t* offsets_dev, int64_t* total) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return radius_count_locked(c, problems, n, max_distance, offsets_dev, total);
+}
+
+mim_status mim_radius_fill_dev(mim_ctx* c, int32_t* idx_dev, float* dist_dev, int64_t cap) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return radius_fill_locked(c, idx_dev, dist_dev, cap);
+}
+
+mim_status mim_radius_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
+                         float max_distance, int64_t* offsets, int32_t* idx, float* dist, int64_t cap) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || !offsets || (nq > 0 && !q) || (nt > 0 && !t) || (idx && !dist) || cap < 0)
+        return fail(c, MIM_EINVAL, "radius_l2: bad arguments");
+    if (dim < 1 || dim > kFltMaxDim) return fail(c, MIM_EINVAL, "radius_l2: dim must be 1..%d (got %d)", kFltMaxDim, dim);
+    if (!radius_arg_ok(max_distance))
+        return fail(c, MIM_EINVAL, "radius_l2: max_distance must be above FLT_EPSILON (got %g)", (double)max_distance);
+    offsets[0] = 0;
+    if (nq == 0) return MIM_OK;  // radiusMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> kp0((size_t)std::max(std::max(nq, nt), 1) * 2, 0.f);
+    return radius_host(c, nq, max_distance, offsets, idx, dist, cap, [&](bool query, int32_t* id) {
+        const float* rows = query ? q : t;
+        const int n = query ? nq : nt;
+        // dim 128: the 128-D path, so that integer rows take the MFMA kernel (the same bits either way)
+        if (dim == kDim) return set_create_locked(c, rows ? rows : kp0.data(), kp0.data(), n, dim, 0, id);
+        return set_create_f32_locked(c, rows, (int64_t)4 * dim, kp0.data(), n, dim, 0, id);
+    });
+}
+
+mim_status mim_radius_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
+                              float max_distance, int64_t* offsets, int32_t* idx, float* dist, int64_t cap) {
+    if (!c) return MIM_EINVAL;
+    if (nq < 0 || nt < 0 || !offsets || (nq > 0 && !q) || (nt > 0 && !t) || (idx && !dist) || cap < 0)
+        return fail(c, MIM_EINVAL, "radius_hamming: bad arguments");
+    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "radius_hamming: width must be 1..64 bytes (got %d)", width);
+    if (!radius_arg_ok(max_distance))
+        return fail(c, MIM_EINVAL, "radius_hamming: max_distance must be above FLT_EPSILON (got %g)", (double)max_distance);
+    offsets[0] = 0;
+    if (nq == 0) return MIM_OK;  // radiusMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> kp0((size_t)std::max(std::max(nq, nt), 1) * 2, 0.f);
+    return radius_host(c, nq, max_distance, offsets, idx, dist, cap, [&](bool query, int32_t* id) {
         return set_create_bin_locked(c, query ? q : t, width, kp0.data(), query ? nq : nt, width, 0, id);
     });
 }

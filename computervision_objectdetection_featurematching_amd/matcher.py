@@ -690,6 +690,107 @@ class Matcher:
         self._check(self.L.mim_knn_batch_dev(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr), k,
                                              C.c_void_p(_lib.ptr(idx_dev)), C.c_void_p(_lib.ptr(dist_dev))))
 
+    # ---- radiusMatch ----------------------------------------------------------
+    @staticmethod
+    def _check_radius(max_distance) -> float:
+        r = float(np.float32(max_distance))
+        if not r > float(np.finfo(np.float32).eps):  # DescriptorMatcher::radiusMatch's CV_Assert; a NaN fails
+            raise ValueError(f"radiusMatch: maxDistance must be above FLT_EPSILON (got {max_distance!r})")
+        return r
+
+    def _radius_host(self, fn, q, t, max_distance):
+        """Offsets first (idx NULL), then the lists into buffers of exactly that size."""
+        r = self._check_radius(max_distance)
+        nq = q.shape[0]
+        offsets = np.zeros(nq + 1, np.int64)
+        args = (self._ctx, C.c_void_p(q.ctypes.data), nq, C.c_void_p(t.ctypes.data), t.shape[0], q.shape[1], r,
+                C.c_void_p(offsets.ctypes.data))
+        self._check(fn(*args, None, None, 0))
+        total = int(offsets[nq])
+        idx, dist = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.float32)
+        if total:
+            self._check(fn(*args, C.c_void_p(idx.ctypes.data), C.c_void_p(dist.ctypes.data), total))
+        return offsets, idx[:total], dist[:total]
+
+    @staticmethod
+    def _radius_dmatches(offsets, idx, dist):
+        """radiusMatch's list of lists from the CSR arrays."""
+        return [[DMatch(i, int(idx[j]), 0, float(dist[j])) for j in range(int(offsets[i]), int(offsets[i + 1]))]
+                for i in range(len(offsets) - 1)]
+
+    def radius_match_arrays(self, query, train, max_distance):
+        """BFMatcher(NORM_L2).radiusMatch(query, train, maxDistance) on 128-D float rows as CSR arrays (mim_radius_l2
+        at dim 128: integer-valued rows on the i8 MFMA kernel): offsets int64 (nq + 1), idx int32, dist float32,
+        query i's matches at [offsets[i], offsets[i + 1]), ascending in (distance, train index)."""
+        q = np.ascontiguousarray(query, np.float32).reshape(-1, DIM)
+        t = np.ascontiguousarray(train, np.float32).reshape(-1, DIM)
+        return self._radius_host(self.L.mim_radius_l2, q, t, max_distance)
+
+    def radius_match(self, query, train, max_distance):
+        """BFMatcher(NORM_L2).radiusMatch(query, train, matches, maxDistance) -> list of lists of DMatch."""
+        return self._radius_dmatches(*self.radius_match_arrays(query, train, max_distance))
+
+    def radius_match_hamming_arrays(self, query, train, max_distance):
+        """BFMatcher(NORM_HAMMING).radiusMatch on uint8 rows of one width (1..64 bytes) as CSR arrays
+        (mim_radius_hamming); outputs as radius_match_arrays."""
+        q, t = np.asarray(query), np.asarray(train)
+        if q.dtype != np.uint8 or t.dtype != np.uint8 or q.ndim != 2 or t.ndim != 2:
+            raise ValueError("radius_match_hamming: uint8 (n, width) arrays are required")
+        if q.shape[1] != t.shape[1]:
+            raise ValueError(f"radius_match_hamming: query rows of {q.shape[1]} bytes, train rows of {t.shape[1]}")
+        return self._radius_host(self.L.mim_radius_hamming, np.ascontiguousarray(q), np.ascontiguousarray(t), max_distance)
+
+    def radius_match_hamming(self, query, train, max_distance):
+        """BFMatcher(NORM_HAMMING).radiusMatch(query, train, matches, maxDistance) -> list of lists of DMatch."""
+        return self._radius_dmatches(*self.radius_match_hamming_arrays(query, train, max_distance))
+
+    def radius_match_float_arrays(self, query, train, max_distance):
+        """BFMatcher(NORM_L2).radiusMatch on float32 rows of one dim 1..512 as CSR arrays (mim_radius_l2); outputs
+        as radius_match_arrays."""
+        q, t = np.asarray(query), np.asarray(train)
+        if q.dtype != np.float32 or t.dtype != np.float32 or q.ndim != 2 or t.ndim != 2:
+            raise ValueError("radius_match_float: float32 (n, dim) arrays are required")
+        if q.shape[1] != t.shape[1]:
+            raise ValueError(f"radius_match_float: query rows of dim {q.shape[1]}, train rows of dim {t.shape[1]}")
+        return self._radius_host(self.L.mim_radius_l2, np.ascontiguousarray(q), np.ascontiguousarray(t), max_distance)
+
+    def radius_match_float(self, query, train, max_distance):
+        """BFMatcher(NORM_L2).radiusMatch(query, train, matches, maxDistance) on float rows of any dim -> lists of
+        DMatch."""
+        return self._radius_dmatches(*self.radius_match_float_arrays(query, train, max_distance))
+
+    def radius_batch(self, problems, max_distance):
+        """radiusMatch of every problem (query set, train set) of any mix of kinds: mim_radius_count, then the
+        allocation, then mim_radius_fill_dev.  Returns (offsets int64, idx int32, dist float32) as device tensors,
+        CSR over all queries of all problems in order.  The fill is asynchronous on the matcher's stream; torch's
+        current stream is ordered after it, so the tensors can be used there at once."""
+        import torch
+        r = self._check_radius(max_distance)
+        arr = problems if isinstance(problems, np.ndarray) else np.asarray(list(problems), np.int32)
+        arr = np.ascontiguousarray(arr, np.int32).reshape(-1, 2)
+        nq = 0
+        for qs in arr[:, 0]:
+            rows = self._set_rows.get(int(qs))
+            if rows is None:
+                raise ValueError(f"radius_batch: the row count of set {int(qs)} is not known here")
+            nq += rows
+        dev = torch.device("cuda", self.device)
+        offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the zero fill, before the matcher's stream writes
+        total = C.c_int64()
+        self._check(self.L.mim_radius_count(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr), r,
+                                            C.c_void_p(offsets.data_ptr()), C.byref(total)))
+        idx = torch.empty(max(total.value, 1), dtype=torch.int32, device=dev)
+        dist = torch.empty(max(total.value, 1), dtype=torch.float32, device=dev)
+        self._check(self.L.mim_radius_fill_dev(self._ctx, C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()),
+                                               total.value))
+        torch.cuda.current_stream(dev).wait_stream(torch.cuda.ExternalStream(self.stream_handle(), device=dev))
+        return offsets, idx[:total.value], dist[:total.value]
+
+    def radius_sets(self, qset: int, tset: int, max_distance):
+        """radius_batch of the one problem (qset, tset)."""
+        return self.radius_batch([(int(qset), int(tset))], max_distance)
+
     def set_sampler_stream(self, on: bool):
         """Second-stream getSubset replay (mim_ctx_set_sampler_stream): on for a batch alone, off when
         several contexts already overlap their batches."""

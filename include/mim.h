@@ -293,6 +293,41 @@ mim_status mim_knn_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const flo
 mim_status mim_knn_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
                            int32_t width, int32_t k, int32_t* idx, float* dist);
 
+/* ---- radiusMatch (BFMatcher(norm).radiusMatch(q, t, matches, maxDistance)) -----------------------
+ * For every query row every train row with DMatch::distance <= max_distance, the test being the float32
+ * compare of the distance against the float max_distance (a NaN distance never matches, an overflowed +inf
+ * distance only max_distance = +inf), sorted ascending under (distance as float32, train index): std::sort
+ * leaves the order of equal distances open, the lower index first is one of the orders it may produce and the
+ * tie rule of every other entry here.  The distances carry the bits of the k = 2 entries of the kind (the
+ * popcount as float; sqrtf of the squared distance in OpenCV's summation order, exact for integer 128-D rows).
+ * max_distance must be above FLT_EPSILON (DescriptorMatcher::radiusMatch's CV_Assert); anything else, a NaN
+ * included, is MIM_EINVAL.  The result is CSR over all queries of all problems in order: offsets has
+ * nq_0 + ... + nq_{n-1} + 1 int64 entries, query j's matches are idx / dist [offsets[j], offsets[j + 1]).
+ * Problems without queries or train rows, queries without a match and n = 0 are all valid.  Like the other
+ * primitives these calls leave the ctx without a batch (mim_batch_results returns no records).
+ *
+ * mim_radius_count: the count pass and the scan over n problems of registered sets, any mix of kinds, with
+ * the pairing rules and errors of mim_batch_run (as mim_knn_batch_dev).  Waits for the one scalar *total =
+ * offsets[last], the entries the caller's idx / dist need; offsets_dev (device memory, may be NULL) receives
+ * the offsets. */
+mim_status mim_radius_count(struct mim_ctx* ctx, const mim_problem* problems, int32_t n, float max_distance,
+                            int64_t* offsets_dev, int64_t* total);
+/* The fill pass, the per-query sort and the split into idx_dev / dist_dev (device buffers of cap entries) of
+ * the LAST mim_radius_count on this ctx, asynchronous on the ctx stream.  MIM_EINVAL when there is no such
+ * call, or when sets were cleared or truncated since; MIM_ERANGE for cap < total (nothing is written);
+ * MIM_ENOMEM when the internal key or merge buffer cannot be allocated. */
+mim_status mim_radius_fill_dev(struct mim_ctx* ctx, int32_t* idx_dev, float* dist_dev, int64_t cap);
+/* Host buffers, synchronous: dense CV_32F rows of any dim 1..512.  offsets: nq + 1 entries; idx / dist: cap
+ * entries.  idx NULL: the offsets only; offsets[nq] > cap: MIM_ERANGE, the offsets are valid and nothing else
+ * is written.  dim 128 goes through the sets of mim_set_create, so integer-valued rows take the exact i8 MFMA
+ * kernel; any other dim (and non-integer rows) the float kernel: the same bits either way. */
+mim_status mim_radius_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
+                         float max_distance, int64_t* offsets, int32_t* idx, float* dist, int64_t cap);
+/* Host buffers, synchronous: dense CV_8U rows of `width` bytes, 1..64; outputs as mim_radius_l2. */
+mim_status mim_radius_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
+                              int32_t width, float max_distance, int64_t* offsets, int32_t* idx, float* dist,
+                              int64_t cap);
+
 /* ---- feature extraction either side of the matcher ---------------------------
  * cv::KeyPoint without class_id; octave packed as OpenCV packs it (octave & 255 | layer << 8 |
  * sub-layer << 16, octave -1 for the doubled image). */
