@@ -761,6 +761,7 @@ void orc_match_problem(const float* qdesc, const float* qkp, int nq, const float
             memset(mask, 1, 4);
             ok = orc_run_kernel(src, dst, 4, res->H) > 0;
             res->iters = 0;
+            if (!ok) memset(mask, 0, 4); /* findHomography: tempMask = zeros when there is no model */
         } else {
             int it = 0;
             ok = orc_ransac(src, dst, ng, prm->ransac_thresh, prm->confidence, prm->max_iters,
