@@ -222,7 +222,7 @@ constexpr int kEarlyTiles = MIM_KNN_EARLY;
 // row can enter that top-2 only if D <= Dc, the 2nd smallest of the pair's four D (an equal D may
 // still win on the lower index), and a row that does enters its own lane's list, so the filter
 // keeps the invariant.  D = 2R + p with p in {0,1} gives R <= floor(Dc/2).
-// o1 <= o2: the partner lane's m1, m2 (exchanged by permlane32_swap once per stage; the partner's
+// o1 <= o2: the partner lane's m1, m2 (exchanged by permlane32_swap at each refresh; the partner's
 // values only decrease, so a stale copy gives a threshold >= the exact one: still a superset).
 __device__ __forceinline__ int late_threshold(const LaneSel& s, int o1, int o2) {
     return min(max(s.m1, o1), min(s.m2, o2)) >> 1;  // 2nd smallest of {m1 <= m2, o1 <= o2}, halved
@@ -260,6 +260,27 @@ __device__ __forceinline__ int med3_i32(int a, int b, int c) {
 // the same time (MI355X_MICROARCH.md, "try a stagger")
 #ifndef MIM_KNN_STAGGER
 #define MIM_KNN_STAGGER 0
+#endif
+// refresh schedule of the late loop: every stage for the first MIM_KNN_REFRESH_DENSE late stages of a
+// sweep, after that on every MIM_KNN_REFRESH_EVERY-th late stage, counted from the first late stage (so a
+// work item starting at any tile behaves the same).  EVERY = 1: every stage, the code without a schedule.
+#ifndef MIM_KNN_REFRESH_DENSE
+#define MIM_KNN_REFRESH_DENSE 8
+#endif
+#ifndef MIM_KNN_REFRESH_EVERY
+#define MIM_KNN_REFRESH_EVERY 4
+#endif
+constexpr int kRefreshDense = MIM_KNN_REFRESH_DENSE, kRefreshEvery = MIM_KNN_REFRESH_EVERY;
+static_assert(kRefreshDense >= 0 && kRefreshEvery >= 1, "refresh schedule");
+// MFMA order inside a 32-row block: 0 k-step major (both column tiles' chains end together), 1 column-tile
+// major (the four k-steps of column tile 0, then those of tile 1: tile 0's filter can start under them)
+#ifndef MIM_KNN_MFMA_ORDER
+#define MIM_KNN_MFMA_ORDER 0
+#endif
+// a wave whose queries all lie past the set (qbase >= nq) only stages and keeps the barriers; 0: it
+// runs the whole sweep on padding, as every wave did before
+#ifndef MIM_KNN_SKIP_PAD
+#define MIM_KNN_SKIP_PAD 1
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -357,6 +378,27 @@ struct KnnRatioArg<2> {
 // i1 by V4.  Anything else (the two differ, or a passing first value is tracked) is marked for
 // knn2_rescan_kernel, which rewrites the record from the fp32 rows.  Padded rows (R = 2^30 - 1) are never
 // under a limit, and their tile caps mn before the shift; a lane half has real rows from the early tiles.
+// (A padded row is still pushed, in every mode, when another lane hits its accumulator slot of the last
+// tile: its D = INT_MAX never displaces a real value, and the verdict mode's push caps it before doubling.)
+//
+// Refresh schedule (MIM_KNN_REFRESH_DENSE, MIM_KNN_REFRESH_EVERY): a stage off the schedule exchanges
+// nothing and computes no limit; o1c, o2c and T[u] stay what the last refresh and the events since left.
+// Nothing above depends on when a refresh happens, only on what a limit was taken from:
+//   exact mode: a lane's own values change only in events, which recompute T from them and the partner
+//   copy; the copy is stale upwards, so T is at least the exact threshold: a superset, for any staleness.
+//   ratio mode: a failing limit v = Q1r is justified row by row from the refresh's pair (Q1r, Q2r) for as
+//   long as the lane is not refreshed again, however many stages that is; a candidate limit only falls, in
+//   events, and a stale partner copy only raises it.  The invariant is kept by every row, so it holds at the
+//   end of the sweep whichever stages refreshed.
+//   verdict mode: V1 and V2 come from the tracked push of every half tile, which no schedule skips.  V3's
+//   flip-limit case runs from the refresh that took Q1r to the lane's next hit, over any number of stages; a
+//   candidate limit taken earlier stands for a larger e_hi(Q2) than the current one (tracked rows lower the
+//   values without an event), so it only admits more rows, which are pushed exactly.  V4 needs X under its
+//   lane's limit: D(X) < G2 <= e_hi(Q2) now <= e_hi(Q2) then, and under a flip limit the same inequality
+//   against Q1r.  V5 follows from V3.
+// What a skipped refresh costs is events, never a verdict: a pair that turned surely failing since the last
+// refresh keeps its candidate limit until the next one (a failing lane that hits turns candidate in the event
+// itself, so the reverse needs no refresh).  The first late stage of a work item always refreshes.
 template <int MODE>  // 0 exact, 1 ratio mode, 2 verdict mode
 __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC = waves per SIMD
     const ProbDev* __restrict__ probs, const KnnWork* __restrict__ works, const int* __restrict__ seg_start,
@@ -406,19 +448,24 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
 
     // ---- query fragments q': column tile u = query rows qbase + 32u .. + 31 ----
     const int qbase = w.q0 + wave * 32 * QT;
+    // a wave of padding only (wave-uniform, decided on the scalar unit): no fragments, tiles, refreshes
+    // or epilogue; it stages its share of every stage and meets every barrier
+    const bool live = !MIM_KNN_SKIP_PAD || w.q0 + __builtin_amdgcn_readfirstlane(wave) * 32 * QT < nq;
     i32x4 B[QT][4];
+    if (live) {
 #pragma unroll
-    for (int u = 0; u < QT; ++u) {
-        const int qr = qbase + 32 * u, qt = qr >> 6, qh = (qr >> 5) & 1;
-        const bool ok = qt < P->q.n_tiles;
-        const int qtc = ok ? qt : 0;  // rows past the set: loaded from tile 0, never written out
-        const gi32x4* qsrc = (const gi32x4*)(P->q.frag) + (size_t)qtc * 512;
+        for (int u = 0; u < QT; ++u) {
+            const int qr = qbase + 32 * u, qt = qr >> 6, qh = (qr >> 5) & 1;
+            const bool ok = qt < P->q.n_tiles;
+            const int qtc = ok ? qt : 0;  // rows past the set: loaded from tile 0, never written out
+            const gi32x4* qsrc = (const gi32x4*)(P->q.frag) + (size_t)qtc * 512;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) B[u][s] = ~qsrc[(qh * 4 + s) * 64 + lane];  // q' = ~t''
+            for (int s = 0; s < 4; ++s) B[u][s] = ~qsrc[(qh * 4 + s) * 64 + lane];  // q' = ~t''
+        }
     }
     LaneSel st[QT];
     int T[QT];  // late-tile thresholds on R
-    // the partner lane's (l ^ 32) m1, m2 as of the last refresh (every stage): between refreshes an
+    // the partner lane's (l ^ 32) m1, m2 as of the last refresh (the schedule above): between refreshes an
     // insertion recomputes the threshold from its own fresh pair and these (the partner's values only
     // decrease, so a stale copy gives a threshold >= the exact one: a superset, no exchange per event)
     int o1c[QT], o2c[QT];
@@ -444,7 +491,10 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
         else T[u] = late_threshold(st[u], o1c[u], o2c[u]);
     };
     auto push = [&](int u, int v, int idx) {
-        if (FLIP) sel_push_r(st[u], v << 1, idx);  // exact values are stored as 2 D
+        // exact values are stored as 2 D.  A padded row (D = INT_MAX) is pushed too when another lane hits
+        // the same accumulator slot of the last tile: capped so that doubling it cannot wrap to -2, which
+        // would become the minimum of every query of the column tile whose other lane half holds it
+        if (FLIP) sel_push_r(st[u], min(v, INT_MAX >> 1) << 1, idx);
         else if (RATIO) sel_push_r(st[u], v, idx);
         else sel_push(st[u], v, idx);
     };
@@ -505,6 +555,16 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
         }
 #pragma unroll
         for (int u = 1; u < QT; ++u) acc[u] = acc[0];
+        if (MIM_KNN_MFMA_ORDER == 1) {
+            i32x4 a[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) a[s] = A[(u2 * 4 + s) * 64 + lane];
+#pragma unroll
+            for (int u = 0; u < QT; ++u)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc[u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], B[u][s], acc[u], 0, 0, 0);
+            return;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const i32x4 a = A[(u2 * 4 + s) * 64 + lane];
@@ -713,21 +773,26 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
         const unsigned char* sb = smem + buf * kStage * kLdsTile;
 #pragma unroll
         for (int ts = 0; ts < kStage; ++ts)
-            if (kStage == 1 || stage + ts < w.tile1) tile_early(sb + ts * kLdsTile, stage + ts);
+            if (live && (kStage == 1 || stage + ts < w.tile1)) tile_early(sb + ts * kLdsTile, stage + ts);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA into the next buffer landed
         __syncthreads();
     }
-    for (; stage < w.tile1; stage += kStage) {
+    for (int ls = 0; stage < w.tile1; stage += kStage, ++ls) {  // ls: the sweep's late stages, counted from 0
         const int buf = ((stage - w.tile0) / kStage) & 1;
         const bool more = stage + kStage < w.tile1;
+        // a stage off the refresh schedule skips what only feeds refresh(): the c(q) read, the exchange
+        // (o1c, o2c keep their last values) and the limit arithmetic; T[u] stays as the last refresh and
+        // the events since left it.  The first late stage (ls = 0) always refreshes.
+        const bool fresh = kRefreshEvery == 1 || ls < kRefreshDense || ls % kRefreshEvery == 0;
         // c(q) for the refresh, read before the next stage's DMA is issued: an LDS read after it
         // would wait for that DMA (the waitcnt pass cannot tell the words apart)
         int cqv[QT];
+        if (live && fresh) {
 #pragma unroll
-        for (int u = 0; u < QT; ++u) cqv[u] = RATIO ? cq[32 * u] : 0;
+            for (int u = 0; u < QT; ++u) cqv[u] = RATIO ? cq[32 * u] : 0;
+        }
         if (more) stage_dma(stage + kStage, buf ^ 1, false);
         const unsigned char* sb = smem + buf * kStage * kLdsTile;
-        flush_deferred();  // the previous stage's last half tile (waves 4-7 with MIM_KNN_STAGGER)
         auto refresh = [&]() {  // thresholds from the partner lane's current m1, m2 (every tile: slower, r03bd)
 #pragma unroll
             for (int u = 0; u < QT; ++u) {
@@ -757,18 +822,22 @@ __global__ __launch_bounds__(kThreads, MIM_KNN_OCC) void knn2_i8_kernel(  // OCC
                 }
             }
         };
-        refresh();
-        // rolled by default (unrolling measured no faster; the late tile is ~3 KiB of code)
+        if (live) {
+            flush_deferred();  // the previous stage's last half tile (waves 4-7 with MIM_KNN_STAGGER)
+            if (fresh) refresh();
+            // rolled by default (unrolling measured no faster; the late tile is ~3 KiB of code)
 #pragma unroll MIM_KNN_LATE_UNROLL
-        for (int ts = 0; ts < kStage; ++ts)
-            if (kStage == 1 || stage + ts < w.tile1)
-                tile_late(sb + ts * kLdsTile, stage + ts, stagger && (ts == kStage - 1 || stage + ts + 1 == w.tile1));
+            for (int ts = 0; ts < kStage; ++ts)
+                if (kStage == 1 || stage + ts < w.tile1)
+                    tile_late(sb + ts * kLdsTile, stage + ts, stagger && (ts == kStage - 1 || stage + ts + 1 == w.tile1));
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA into the next buffer landed
         __syncthreads();
     }
     flush_deferred();
 
     // ---- merge the two lane halves (disjoint train rows of the same query), keys ----
+    if (!live) continue;  // nothing to store (q >= nq in every lane); the next item's barriers come after
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
         LaneSel m = st[u];
