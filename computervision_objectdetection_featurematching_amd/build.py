@@ -34,10 +34,9 @@ def needs_build() -> bool:
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    deps = sources() + [os.path.join(CSRC, "mim_internal.h"), os.path.join(CSRC, "knn_schedule.h"),
-                        os.path.join(CSRC, "mim_debug.h"), os.path.join(CSRC, "knn_float_arith.h"),
-                        os.path.join(CSRC, "knn_topk_merge.h"), os.path.join(CSRC, "radius.h"),
-                        os.path.join(CSRC, "radius_host.h"), os.path.join(HERE, "..", "include", "mim.h")]
+    # every header under csrc/, so that a new one cannot be forgotten here
+    deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    deps.append(os.path.join(HERE, "..", "include", "mim.h"))
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

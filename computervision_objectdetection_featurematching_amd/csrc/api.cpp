@@ -14,7 +14,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -123,6 +122,12 @@ struct SetRec {
     int bin_width = 0; // binary set: the caller's bytes per row
     int fdim = 0;      // generic float set (mim_set_create_f32): floats per row, 1..kFltMaxDim; 0: not one
     int fpad = 0;      // generic float set: floats per stored row (fdim rounded up to a multiple of 4)
+    // the kind, and what the float kernels read of a generic float or a 128-D set (no caller decodes the fields)
+    bool is_bin() const { return bin_pad != 0; }
+    bool is_f32() const { return fdim != 0; }
+    bool is_sift() const { return !bin_pad && !fdim; }  // the 128-D set of mim_set_create, with its prep job
+    int flt_dim() const { return fdim ? fdim : kDim; }
+    int flt_stride() const { return fdim ? fpad : kDim; }
 };
 
 // Pinned staging for the per-batch tables, two generations: a batch's host->device table copies
@@ -168,6 +173,30 @@ struct PinnedStage {
             ev[i] = nullptr;
         }
     }
+};
+
+template <class T> size_t vec_bytes(const std::vector<T>& v) { return sizeof(T) * v.size(); }
+
+// One call's table uploads through a PinnedStage generation of `total` bytes: put() copies a table into the
+// stage behind the last one and enqueues its host->device copy, done() lets the generation go after them.
+// The first error sticks, so only done()'s result needs a check.
+struct StageWriter {
+    PinnedStage& ps;
+    hipStream_t s;
+    char* p = nullptr;
+    size_t off = 0;
+    hipError_t err;
+    StageWriter(PinnedStage& ps_, size_t total, hipStream_t s_) : ps(ps_), s(s_) { err = ps.acquire(total, &p); }
+    // b: a second table that lies behind the first on the device too (one copy for both)
+    void put(void* dst, const void* a, size_t ab, const void* b = nullptr, size_t bb = 0) {
+        if (err != hipSuccess || ab + bb == 0) return;
+        if (ab) memcpy(p + off, a, ab);
+        if (bb) memcpy(p + off + ab, b, bb);
+        err = hipMemcpyAsync(dst, p + off, ab + bb, hipMemcpyHostToDevice, s);
+        off += ab + bb;
+    }
+    template <class T> void put(const DevBuf& dst, const std::vector<T>& v) { put(dst.p, v.data(), vec_bytes(v)); }
+    hipError_t done() { return err != hipSuccess ? err : ps.release_after(s); }
 };
 
 }  // namespace
@@ -289,6 +318,21 @@ static mim_status fail(mim_ctx* c, mim_status code, const char* fmt, ...) {
             return fail((c), e_ == hipErrorOutOfMemory ? MIM_ENOMEM : MIM_EDEVICE, "%s: %s (%s:%d)", \
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                       \
     } while (0)
+
+// no RANSAC records: the previous batch's are invalidated (mim.h)
+static void invalidate_batch(mim_ctx* c) {
+    c->last_n = 0;
+    c->last_gen = -1;
+    c->last_fh = false;
+}
+
+// The row arguments every host-buffer entry takes; outputs_ok: the entry's own test of its output pointers.
+static mim_status check_host_pair(mim_ctx* c, const char* entry, const void* q, int32_t nq, const void* t, int32_t nt,
+                                  bool outputs_ok) {
+    if (nq < 0 || nt < 0 || (nq > 0 && !q) || (nt > 0 && !t) || !outputs_ok)
+        return fail(c, MIM_EINVAL, "%s: bad arguments", entry);
+    return MIM_OK;
+}
 
 extern "C" {
 
@@ -452,11 +496,9 @@ static mim_status flush_preps(mim_ctx* c) {
     }
     const size_t bytes = sizeof(PrepJob) * nj;
     HIPCHK(c, c->prep_jobs.ensure(bytes));
-    char* st = nullptr;
-    HIPCHK(c, c->prep_stage.acquire(bytes, &st));
-    memcpy(st, c->pend.data(), bytes);
-    HIPCHK(c, hipMemcpyAsync(c->prep_jobs.p, st, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, c->prep_stage.release_after(c->stream));
+    StageWriter up(c->prep_stage, bytes, c->stream);
+    up.put(c->prep_jobs, c->pend);
+    HIPCHK(c, up.done());
     launch_prep_batch(c->prep_jobs.as<PrepJob>(), nj, tiles, c->stream);
     HIPCHK(c, hipGetLastError());
     c->flushes.push_back({*std::min_element(c->pend_set.begin(), c->pend_set.end()), c->arena.pos()});
@@ -472,22 +514,15 @@ mim_status mim_set_create(mim_ctx* c, const float* desc, const float* kp, int32_
     return set_create_locked(c, desc, kp, n, dim, on_device, set_id);
 }
 
-// A binary set: rows copied into the library's own storage (never borrowed), zero-padded to 16, 32 or
-// 64 bytes, with zero rows up to the next multiple of kHamTileRows (the Hamming kernel stages whole
-// tiles).  No prep job: the kernel reads the padded rows as they are.
-static mim_status set_create_bin_locked(mim_ctx* c, const uint8_t* desc, int64_t step, const float* kp, int32_t n,
-                                        int32_t width, int32_t on_device, int32_t* set_id) {
-    if (!set_id || n < 0 || (n > 0 && (!desc || !kp))) return fail(c, MIM_EINVAL, "set_create_bin: bad arguments");
-    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "set_create_bin: width must be 1..64 bytes (got %d)", width);
-    if (step < width)
-        return fail(c, MIM_EINVAL, "set_create_bin: step %lld < width %d", (long long)step, width);
+// The sets that keep a copy of the caller's rows and need no prep job (binary, generic float): n rows of
+// row_bytes at `step` copied to a stride of stored_bytes, zero filled, with zero rows up to the next multiple
+// of row_pad (the kernels stage whole tiles).  r says the kind; `who` names the entry in the messages.
+static mim_status set_create_rows_locked(mim_ctx* c, const char* who, SetRec r, const void* desc, int64_t step,
+                                         size_t row_bytes, size_t stored_bytes, int row_pad, const float* kp, int32_t n,
+                                         int32_t on_device, int32_t* set_id) {
     HIPCHK(c, hipSetDevice(c->device));
-    const int pad = width <= 16 ? 16 : width <= 32 ? 32 : 64;
-    const size_t rows = (size_t)std::max((n + kHamTileRows - 1) / kHamTileRows, 1) * kHamTileRows;
-    SetRec r{};
+    const size_t bytes = (size_t)std::max((n + row_pad - 1) / row_pad, 1) * row_pad * stored_bytes;
     r.mark = c->arena.pos();
-    r.bin_pad = pad;
-    r.bin_width = width;
     r.d.n = n;
     r.d.n_tiles = (n + 63) / 64;
     void *dd = nullptr, *dk = nullptr;
@@ -495,23 +530,39 @@ static mim_status set_create_bin_locked(mim_ctx* c, const uint8_t* desc, int64_t
         c->arena.seek(r.mark);
         return st;
     };
-    if (c->arena.alloc(rows * pad, &dd) != hipSuccess || c->arena.alloc((size_t)std::max(n, 1) * sizeof(float2), &dk) != hipSuccess)
-        return undo(fail(c, MIM_ENOMEM, "set_create_bin: device allocation of %zu bytes failed", rows * pad));
+    if (c->arena.alloc(bytes, &dd) != hipSuccess ||
+        c->arena.alloc((size_t)std::max(n, 1) * sizeof(float2), &dk) != hipSuccess)
+        return undo(fail(c, MIM_ENOMEM, "%s: device allocation of %zu bytes failed", who, bytes));
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    hipError_t e = hipMemsetAsync(dd, 0, rows * pad, c->stream);
+    hipError_t e = hipMemsetAsync(dd, 0, bytes, c->stream);
     if (e == hipSuccess && n > 0)
-        e = hipMemcpy2DAsync(dd, (size_t)pad, desc, (size_t)step, (size_t)width, (size_t)n, kind, c->stream);
+        e = hipMemcpy2DAsync(dd, stored_bytes, desc, (size_t)step, row_bytes, (size_t)n, kind, c->stream);
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dk, kp, (size_t)n * sizeof(float2), kind, c->stream);
     if (e == hipSuccess && !on_device) e = hipStreamSynchronize(c->stream);  // host buffers may go away
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        return undo(fail(c, MIM_EDEVICE, "set_create_bin: copy failed: %s", hipGetErrorString(e)));
+        return undo(fail(c, MIM_EDEVICE, "%s: copy failed: %s", who, hipGetErrorString(e)));
     }
-    r.d.frag = (const int8_t*)dd;
+    if (r.is_bin()) r.d.frag = (const int8_t*)dd;
+    else r.d.f32 = (const float*)dd;
     r.d.kp = (const float2*)dk;
     *set_id = (int32_t)c->sets.size();
     c->sets.push_back(r);
     return MIM_OK;
+}
+
+// A binary set: rows zero-padded to 16, 32 or 64 bytes, which the Hamming kernel reads as they are.
+static mim_status set_create_bin_locked(mim_ctx* c, const uint8_t* desc, int64_t step, const float* kp, int32_t n,
+                                        int32_t width, int32_t on_device, int32_t* set_id) {
+    if (!set_id || n < 0 || (n > 0 && (!desc || !kp))) return fail(c, MIM_EINVAL, "set_create_bin: bad arguments");
+    if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "set_create_bin: width must be 1..64 bytes (got %d)", width);
+    if (step < width)
+        return fail(c, MIM_EINVAL, "set_create_bin: step %lld < width %d", (long long)step, width);
+    SetRec r{};
+    r.bin_pad = width <= 16 ? 16 : width <= 32 ? 32 : 64;
+    r.bin_width = width;
+    return set_create_rows_locked(c, "set_create_bin", r, desc, step, (size_t)width, (size_t)r.bin_pad, kHamTileRows,
+                                  kp, n, on_device, set_id);
 }
 
 mim_status mim_set_create_bin(mim_ctx* c, const uint8_t* desc, int64_t step, const float* kp, int32_t n, int32_t width,
@@ -521,10 +572,8 @@ mim_status mim_set_create_bin(mim_ctx* c, const uint8_t* desc, int64_t step, con
     return set_create_bin_locked(c, desc, step, kp, n, width, on_device, set_id);
 }
 
-// A generic float set: rows copied into the library's own storage (never borrowed) at a stride of dim
-// rounded up to 4 floats, zero filled, with zero rows up to the next multiple of kFltRowPad (the float
-// kernel stages whole tiles and never inserts a row past n).  No prep job and no flags: the host knows
-// the kind, so such a set never takes the i8 path.
+// A generic float set: rows at a stride of dim rounded up to 4 floats.  No flags: the host knows the kind,
+// so such a set never takes the i8 path, and the float kernel never inserts a row past n.
 static mim_status set_create_f32_locked(mim_ctx* c, const float* desc, int64_t step, const float* kp, int32_t n,
                                         int32_t dim, int32_t on_device, int32_t* set_id) {
     if (!set_id || n < 0 || (n > 0 && (!desc || !kp))) return fail(c, MIM_EINVAL, "set_create_f32: bad arguments");
@@ -533,39 +582,11 @@ static mim_status set_create_f32_locked(mim_ctx* c, const float* desc, int64_t s
     if (step < (int64_t)4 * dim || step % 4 != 0)
         return fail(c, MIM_EINVAL, "set_create_f32: step %lld must be a multiple of 4 and >= 4 * dim = %d",
                     (long long)step, 4 * dim);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int dp = (dim + 3) & ~3;
-    const size_t rows = (size_t)std::max((n + kFltRowPad - 1) / kFltRowPad, 1) * kFltRowPad;
-    const size_t bytes = rows * dp * sizeof(float);
     SetRec r{};
-    r.mark = c->arena.pos();
     r.fdim = dim;
-    r.fpad = dp;
-    r.d.n = n;
-    r.d.n_tiles = (n + 63) / 64;
-    void *dd = nullptr, *dk = nullptr;
-    auto undo = [&](mim_status st) {
-        c->arena.seek(r.mark);
-        return st;
-    };
-    if (c->arena.alloc(bytes, &dd) != hipSuccess || c->arena.alloc((size_t)std::max(n, 1) * sizeof(float2), &dk) != hipSuccess)
-        return undo(fail(c, MIM_ENOMEM, "set_create_f32: device allocation of %zu bytes failed", bytes));
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    hipError_t e = hipMemsetAsync(dd, 0, bytes, c->stream);
-    if (e == hipSuccess && n > 0)
-        e = hipMemcpy2DAsync(dd, (size_t)dp * sizeof(float), desc, (size_t)step, (size_t)dim * sizeof(float), (size_t)n,
-                             kind, c->stream);
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(dk, kp, (size_t)n * sizeof(float2), kind, c->stream);
-    if (e == hipSuccess && !on_device) e = hipStreamSynchronize(c->stream);  // host buffers may go away
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        return undo(fail(c, MIM_EDEVICE, "set_create_f32: copy failed: %s", hipGetErrorString(e)));
-    }
-    r.d.f32 = (const float*)dd;
-    r.d.kp = (const float2*)dk;
-    *set_id = (int32_t)c->sets.size();
-    c->sets.push_back(r);
-    return MIM_OK;
+    r.fpad = (dim + 3) & ~3;
+    return set_create_rows_locked(c, "set_create_f32", r, desc, step, (size_t)dim * sizeof(float),
+                                  (size_t)r.fpad * sizeof(float), kFltRowPad, kp, n, on_device, set_id);
 }
 
 mim_status mim_set_create_f32(mim_ctx* c, const float* desc, int64_t step, const float* kp, int32_t n, int32_t dim,
@@ -622,9 +643,10 @@ mim_status mim_sets_clear(mim_ctx* c) {
     return MIM_OK;
 }
 
-// drops the sets with ids >= n_keep (0 <= n_keep <= sets.size(), checked by the callers) and
-// rewinds the arena to the first dropped set's storage; with the lock held
-static void sets_truncate_locked(mim_ctx* c, int n_keep) {
+// Drops the sets with ids >= n_keep (0 <= n_keep <= sets.size()) and rewinds the arena to `mark`, the arena
+// before the first dropped set's storage; n_keep == sets.size() drops nothing and only rewinds (what a failed
+// set creation left behind).  The generation stays: callers that change what the user's ids mean bump it.
+static void drop_sets_from(mim_ctx* c, int n_keep, Arena::Mark mark) {
     // the dropped sets' pending preps go; their storage (and prep flags blocks that cover only dropped
     // sets) is reused by later sets, ordered on the ctx stream after the work already enqueued, as
     // for mim_sets_clear
@@ -636,14 +658,18 @@ static void sets_truncate_locked(mim_ctx* c, int n_keep) {
         }
     c->pend.resize(m);
     c->pend_set.resize(m);
-    Arena::Mark target = c->sets[n_keep].mark;
     for (const auto& f : c->flushes)
-        if (f.first < n_keep && target < f.second) target = f.second;  // a kept set's flags lie beyond
+        if (f.first < n_keep && mark < f.second) mark = f.second;  // a kept set's flags lie beyond
     c->flushes.erase(std::remove_if(c->flushes.begin(), c->flushes.end(),
                                     [n_keep](const std::pair<int, Arena::Mark>& f) { return f.first >= n_keep; }),
                      c->flushes.end());
-    c->arena.seek(target);
+    c->arena.seek(mark);
     c->sets.resize(n_keep);
+}
+
+// mim_sets_truncate (n_keep < sets.size(), checked by the callers); with the lock held
+static void sets_truncate_locked(mim_ctx* c, int n_keep) {
+    drop_sets_from(c, n_keep, c->sets[n_keep].mark);
     ++c->sets_gen;
 }
 
@@ -672,9 +698,9 @@ mim_status mim_set_rows(mim_ctx* c, int32_t set_id, int32_t cap, float* desc, fl
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_id < 0 || set_id >= (int)c->sets.size())
         return fail(c, MIM_EINVAL, "set_rows: set %d not registered (%d sets)", set_id, (int)c->sets.size());
-    if (c->sets[set_id].bin_pad)
+    if (c->sets[set_id].is_bin())
         return fail(c, MIM_EINVAL, "set_rows: set %d holds binary descriptors, not float rows", set_id);
-    if (c->sets[set_id].fdim)
+    if (c->sets[set_id].is_f32())
         return fail(c, MIM_EINVAL, "set_rows: set %d holds generic float rows of dim %d, not 128-column rows", set_id,
                     c->sets[set_id].fdim);
     HIPCHK(c, hipSetDevice(c->device));
@@ -720,22 +746,68 @@ static mim_status check_problem_sets(mim_ctx* c, int i, int qs, int ts, bool cro
         return fail(c, MIM_EINVAL, "problem %d: train set of %d rows exceeds OpenCV's 2^18 limit", i,
                     c->sets[ts].d.n);
     const SetRec &Q = c->sets[qs], &T = c->sets[ts];
-    if ((Q.bin_pad != 0) != (T.bin_pad != 0))
+    if (Q.is_bin() != T.is_bin())
         return fail(c, MIM_EINVAL, "problem %d: set %d holds %s descriptors and set %d %s ones", i, qs,
-                    Q.bin_pad ? "binary" : "float", ts, T.bin_pad ? "binary" : "float");
+                    Q.is_bin() ? "binary" : "float", ts, T.is_bin() ? "binary" : "float");
     if (Q.bin_width != T.bin_width)
         return fail(c, MIM_EINVAL, "problem %d: binary sets of different widths (%d and %d bytes)", i, Q.bin_width,
                     T.bin_width);
-    if ((Q.fdim != 0) != (T.fdim != 0))
+    if (Q.is_f32() != T.is_f32())
         return fail(c, MIM_EINVAL, "problem %d: set %d holds %s rows and set %d %s ones", i, qs,
-                    Q.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)", ts,
-                    T.fdim ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
+                    Q.is_f32() ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)", ts,
+                    T.is_f32() ? "generic float (mim_set_create_f32)" : "128-D float (mim_set_create)");
     if (Q.fdim != T.fdim)
         return fail(c, MIM_EINVAL, "problem %d: generic float sets of different dims (%d and %d)", i, Q.fdim, T.fdim);
     if (cross && Q.d.n >= (1 << 18))  // the query set is the reverse direction's train set
         return fail(c, MIM_EINVAL, "problem %d: query set of %d rows exceeds OpenCV's 2^18 limit under a cross-check "
                                    "filter", i, Q.d.n);
     return MIM_OK;
+}
+
+// A call's problem records checked and turned into the schedule's input.  sift_i8: 128-D sets enter as i8
+// problems (the batch); else as float problems at dim 128 (top-k, radius).  qoff: the problems' first rows in
+// the concatenated queries (n + 1 entries).
+struct ProblemList {
+    std::vector<KnnSchedProblem> in;
+    std::vector<long long> qoff;
+    int max_nq = 0;
+};
+static mim_status problem_list(mim_ctx* c, const mim_problem* problems, int n, bool cross, bool sift_i8,
+                               ProblemList& L) {
+    L.in.resize(n);
+    L.qoff.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const int qs = problems[i].query_set, ts = problems[i].train_set;
+        const mim_status s = check_problem_sets(c, i, qs, ts, cross);
+        if (s != MIM_OK) return s;
+        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
+        L.in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.is_bin()};
+        L.in[i].fdim = Q.is_sift() && !sift_i8 ? kDim : Q.fdim;
+        L.qoff[i + 1] = L.qoff[i] + Q.d.n;
+        L.max_nq = std::max(L.max_nq, Q.d.n);
+    }
+    return MIM_OK;
+}
+
+// What every work item of a problem's Hamming pieces shares, and what every one of its float pieces does; the
+// callers add the piece's rows and where its results go.
+struct HamFields {
+    const uint32_t *q, *t;  // the padded rows
+    int nq, wdw;            // query rows, dwords per padded row
+};
+static HamFields ham_fields(const mim_ctx* c, const mim_problem& pr) {
+    const SetRec &Q = c->sets[pr.query_set], &T = c->sets[pr.train_set];
+    return HamFields{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag), Q.d.n,
+                     Q.bin_pad / 4};
+}
+struct FltFields {
+    const float *q, *t;
+    int nq, dim, dp, nt, vec;  // vec: both row pointers are 16-byte aligned (the stride is a multiple of 4 floats)
+};
+static FltFields flt_fields(const mim_ctx* c, const mim_problem& pr) {
+    const SetRec &Q = c->sets[pr.query_set], &T = c->sets[pr.train_set];
+    return FltFields{Q.d.f32, T.d.f32, Q.d.n, Q.flt_dim(), Q.flt_stride(), T.d.n,
+                     (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0 ? 1 : 0};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -752,15 +824,10 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     if (fs != MIM_OK) return fs;
     fs = device_limits(c);
     if (fs != MIM_OK) return fs;
-    std::vector<KnnSchedProblem> in(n);
-    for (int i = 0; i < n; ++i) {
-        const int qs = problems[i].query_set, ts = problems[i].train_set;
-        const mim_status ps = check_problem_sets(c, i, qs, ts, filter != 0);
-        if (ps != MIM_OK) return ps;
-        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
-        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
-        in[i].fdim = Q.fdim;
-    }
+    ProblemList L;
+    fs = problem_list(c, problems, n, filter != 0, true, L);
+    if (fs != MIM_OK) return fs;
+    std::vector<KnnSchedProblem>& in = L.in;
     // cross-check: the shadows join the problem list (binary problems under the fused kernel have none)
     std::vector<int> shadow_of;
     std::vector<mim_problem> ext;
@@ -823,10 +890,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     ham.reserve(S.ham.size());
     for (const HamPiece& hp : S.ham) {
         const ProbDev& P = c->h_probs[hp.problem];
-        const int wdw = c->sets[problems[hp.problem].query_set].bin_pad / 4;
-        const HamWork hw{reinterpret_cast<const uint32_t*>(P.q.frag), reinterpret_cast<const uint32_t*>(P.t.frag),
-                         c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, P.q.n, hp.q0, hp.r0,
-                         hp.r1, wdw, 0};
+        const HamFields f = ham_fields(c, problems[hp.problem]);
+        const HamWork hw{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, f.nq, hp.q0, hp.r0,
+                         hp.r1, f.wdw, 0};
         if (filter != 0 && hp.problem < n_user && shadow_of[hp.problem] < 0)
             hamx.push_back(HamCrossWork{hw, c->colmin.as<uint32_t>() + col_off[hp.problem]});
         else
@@ -839,9 +905,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     flt.reserve(S.flt.size());
     for (const FltPiece& fp : S.flt) {
         const ProbDev& P = c->h_probs[fp.problem];
-        const SetRec& Q = c->sets[problems[fp.problem].query_set];
-        flt.push_back(FltWork{P.q.f32, P.t.f32, c->parts.as<Top2>() + P.part_off + (long long)fp.split * P.q_pad, P.q.n,
-                              fp.q0, fp.r0, fp.r1, Q.fdim, Q.fpad});
+        const FltFields f = flt_fields(c, problems[fp.problem]);
+        flt.push_back(FltWork{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)fp.split * P.q_pad, f.nq, fp.q0,
+                              fp.r0, fp.r1, f.dim, f.dp});
     }
     if (!flt.empty()) HIPCHK(c, c->flt_works.ensure(sizeof(FltWork) * flt.size()));
     HIPCHK(c, c->good_q.ensure(sizeof(int32_t) * good));
@@ -850,36 +916,19 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     HIPCHK(c, c->n_good.ensure(sizeof(int) * std::max(n, 1)));
     HIPCHK(c, c->masks.ensure(good));
     // the device tables are rewritten in stream order (after the previous batch's kernels)
-    const size_t pb = sizeof(ProbDev) * n, wb = sizeof(KnnWork) * works.size(), sb = sizeof(int) * seg.size();
-    const size_t hb = sizeof(HamWork) * ham.size(), fb = sizeof(FltWork) * flt.size();
-    const size_t xb = sizeof(HamCrossWork) * hamx.size(), cb = sizeof(CrossDev) * cross.size();
-    char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + wb + sb + hb + fb + xb + cb, &st));
-    memcpy(st, c->h_probs.data(), pb);
-    memcpy(st + pb, works.data(), wb);
-    memcpy(st + pb + wb, seg.data(), sb);
-    HIPCHK(c, hipMemcpyAsync(c->probs.p, st, pb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->works.p, st + pb, wb + sb, hipMemcpyHostToDevice, c->stream));
-    if (hb) {
-        memcpy(st + pb + wb + sb, ham.data(), hb);
-        HIPCHK(c, hipMemcpyAsync(c->ham_works.p, st + pb + wb + sb, hb, hipMemcpyHostToDevice, c->stream));
-    }
-    if (fb) {
-        memcpy(st + pb + wb + sb + hb, flt.data(), fb);
-        HIPCHK(c, hipMemcpyAsync(c->flt_works.p, st + pb + wb + sb + hb, fb, hipMemcpyHostToDevice, c->stream));
-    }
-    if (xb) {
-        memcpy(st + pb + wb + sb + hb + fb, hamx.data(), xb);
-        HIPCHK(c, hipMemcpyAsync(c->ham_cross_works.p, st + pb + wb + sb + hb + fb, xb, hipMemcpyHostToDevice, c->stream));
-    }
-    if (cb) {
-        memcpy(st + pb + wb + sb + hb + fb + xb, cross.data(), cb);
-        HIPCHK(c, hipMemcpyAsync(c->cross_tab.p, st + pb + wb + sb + hb + fb + xb, cb, hipMemcpyHostToDevice, c->stream));
-    }
+    StageWriter up(c->stage, vec_bytes(c->h_probs) + vec_bytes(works) + vec_bytes(seg) + vec_bytes(ham) + vec_bytes(flt) +
+                                  vec_bytes(hamx) + vec_bytes(cross),
+                   c->stream);
+    up.put(c->probs, c->h_probs);
+    up.put(c->works.p, works.data(), vec_bytes(works), seg.data(), vec_bytes(seg));
+    up.put(c->ham_works, ham);
+    up.put(c->flt_works, flt);
+    up.put(c->ham_cross_works, hamx);
+    up.put(c->cross_tab, cross);
+    HIPCHK(c, up.done());
     c->n_ham_works = (int)ham.size();
     c->n_ham_cross_works = (int)hamx.size();
     c->n_flt_works = (int)flt.size();
-    HIPCHK(c, c->stage.release_after(c->stream));
     c->h_good_off.resize(n_user);
     for (int i = 0; i < n_user; ++i) c->h_good_off[i] = c->h_probs[i].good_off;
     c->last_n = n_user;
@@ -989,27 +1038,28 @@ static mim_status knn_ratio_locked(mim_ctx* c, int n, float ratio, bool emit_knn
     return MIM_OK;
 }
 
-extern "C" {
+// The scope of a host-buffer entry's private sets (mim_knn2_*, mim_knn_*, mim_radius_* on host rows): make_q and
+// make_t append the query and the train set after the user's sets, body runs on the pair, and then, whatever
+// any of them returned, the private sets go with their pending preps and their storage (drop_sets_from), and
+// the batch and radius records that named them are invalidated.  The user's ids and the generation stay.
+template <class MakeQ, class MakeT, class Body>
+static mim_status with_private_sets(mim_ctx* c, MakeQ make_q, MakeT make_t, Body body) {
+    const int base = (int)c->sets.size();
+    const Arena::Mark mark = c->arena.pos();
+    int32_t sq = -1, st = -1;
+    mim_status s = make_q(&sq);
+    if (s == MIM_OK) s = make_t(&st);
+    if (s == MIM_OK) s = body(mim_problem{sq, st});
+    ev_collect(c);
+    drop_sets_from(c, base, mark);
+    invalidate_batch(c);
+    c->rad.valid = false;
+    return s;
+}
 
-mim_status mim_knn2_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
-                       int32_t* idx, float* dist) {
-    if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
-        return fail(c, MIM_EINVAL, "knn2_l2: bad arguments");
-    if (dim != kDim) return fail(c, MIM_EINVAL, "knn2_l2: dim must be %d", kDim);
-    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    // private sets appended after the user's sets, removed afterwards
-    const size_t base = c->sets.size();
-    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
-    int32_t sq, st;
-    mim_status s = set_create_locked(c, q, kp0.data(), nq, dim, 0, &sq);
-    if (s != MIM_OK) return s;
-    s = set_create_locked(c, t ? t : kp0.data(), kp0.data(), nt, dim, 0, &st);
-    if (s != MIM_OK) return s;
-    mim_problem pr{sq, st};
-    s = build_tables(c, &pr, 1, 1);
+// body of the k = 2 host-buffer entries: the batch's distance stage on the one problem, its knnMatch rows back
+static mim_status knn2_host_body(mim_ctx* c, const mim_problem& pr, int nq, int32_t* idx, float* dist) {
+    mim_status s = build_tables(c, &pr, 1, 1);
     if (s != MIM_OK) return s;
     HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * 2 * nq));
     HIPCHK(c, c->knn_dist.ensure(sizeof(float) * 2 * nq));
@@ -1018,100 +1068,55 @@ mim_status mim_knn2_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, i
     HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    ev_collect(c);
-    c->sets.resize(base);  // arena space is reclaimed at the next mim_sets_clear
-    c->last_n = 0;         // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
     return MIM_OK;
+}
+
+extern "C" {
+
+mim_status mim_knn2_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
+                       int32_t* idx, float* dist) {
+    if (!c) return MIM_EINVAL;
+    if (check_host_pair(c, "knn2_l2", q, nq, t, nt, nq <= 0 || (idx && dist)) != MIM_OK) return MIM_EINVAL;
+    if (dim != kDim) return fail(c, MIM_EINVAL, "knn2_l2: dim must be %d", kDim);
+    if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_locked(c, q, kp0.data(), nq, dim, 0, id); },
+        [&](int32_t* id) { return set_create_locked(c, t ? t : kp0.data(), kp0.data(), nt, dim, 0, id); },
+        [&](const mim_problem& pr) { return knn2_host_body(c, pr, nq, idx, dist); });
 }
 
 mim_status mim_knn2_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
                             int32_t* idx, float* dist) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
-        return fail(c, MIM_EINVAL, "knn2_hamming: bad arguments");
+    if (check_host_pair(c, "knn2_hamming", q, nq, t, nt, nq <= 0 || (idx && dist)) != MIM_OK) return MIM_EINVAL;
     if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "knn2_hamming: width must be 1..64 bytes (got %d)", width);
     if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    // private sets appended after the user's sets, removed afterwards (as mim_knn2_l2)
-    const size_t base = c->sets.size();
-    const Arena::Mark mark = c->arena.pos();
     std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
-    // float sets still waiting for their prep get a flags block from the arena at build_tables, after
-    // the private sets' storage: then that storage stays until the next clear, as mim_knn2_l2's does
-    const bool reclaim = c->pend.empty();
-    auto run = [&]() -> mim_status {
-        int32_t sq, st;
-        mim_status s = set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, &sq);
-        if (s != MIM_OK) return s;
-        s = set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, &st);
-        if (s != MIM_OK) return s;
-        mim_problem pr{sq, st};
-        s = build_tables(c, &pr, 1, 1);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * 2 * nq));
-        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * 2 * nq));
-        s = knn_ratio_locked(c, 1, 0.9f, true);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return MIM_OK;
-    };
-    const mim_status s = run();
-    ev_collect(c);
-    // the private sets own their storage and nothing was registered after them: both go
-    c->sets.resize(base);
-    if (reclaim) c->arena.seek(mark);
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
-    return s;
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, id); },
+        [&](int32_t* id) { return set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, id); },
+        [&](const mim_problem& pr) { return knn2_host_body(c, pr, nq, idx, dist); });
 }
 
 mim_status mim_knn2_l2_f32(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
                            int32_t* idx, float* dist) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
-        return fail(c, MIM_EINVAL, "knn2_l2_f32: bad arguments");
+    if (check_host_pair(c, "knn2_l2_f32", q, nq, t, nt, nq <= 0 || (idx && dist)) != MIM_OK) return MIM_EINVAL;
     if (dim < 1 || dim > kFltMaxDim)
         return fail(c, MIM_EINVAL, "knn2_l2_f32: dim must be 1..%d (got %d)", kFltMaxDim, dim);
     if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    // private sets appended after the user's sets, removed afterwards (as mim_knn2_hamming)
-    const size_t base = c->sets.size();
-    const Arena::Mark mark = c->arena.pos();
     std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
-    const bool reclaim = c->pend.empty();  // see mim_knn2_hamming
-    auto run = [&]() -> mim_status {
-        int32_t sq, st;
-        mim_status s = set_create_f32_locked(c, q, (int64_t)4 * dim, kp0.data(), nq, dim, 0, &sq);
-        if (s != MIM_OK) return s;
-        s = set_create_f32_locked(c, t, (int64_t)4 * dim, kp0.data(), nt, dim, 0, &st);
-        if (s != MIM_OK) return s;
-        mim_problem pr{sq, st};
-        s = build_tables(c, &pr, 1, 1);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * 2 * nq));
-        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * 2 * nq));
-        s = knn_ratio_locked(c, 1, 0.9f, true);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return MIM_OK;
-    };
-    const mim_status s = run();
-    ev_collect(c);
-    c->sets.resize(base);
-    if (reclaim) c->arena.seek(mark);
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
-    return s;
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_f32_locked(c, q, (int64_t)4 * dim, kp0.data(), nq, dim, 0, id); },
+        [&](int32_t* id) { return set_create_f32_locked(c, t, (int64_t)4 * dim, kp0.data(), nt, dim, 0, id); },
+        [&](const mim_problem& pr) { return knn2_host_body(c, pr, nq, idx, dist); });
 }
 
 mim_status mim_ratio_filter(mim_ctx* c, const int32_t* idx, const float* dist, int32_t nq, float ratio,
@@ -1161,9 +1166,7 @@ mim_status mim_ratio_filter(mim_ctx* c, const int32_t* idx, const float* dist, i
         if (t_out) HIPCHK(c, hipMemcpy(t_out, c->good_t.p, sizeof(int32_t) * ng, hipMemcpyDeviceToHost));
     }
     *n_good = ng;
-    c->last_n = 0;
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     return MIM_OK;
 }
 
@@ -1183,9 +1186,7 @@ mim_status mim_knn2_sets_dev(mim_ctx* c, int32_t query_set, int32_t train_set, i
     launch_knn_emit(c->probs.as<ProbDev>(), c->h_probs[0].q.n, c->parts.as<Top2>(), idx_dev, dist_dev, c->stream);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "ratio");
-    c->last_n = 0;  // no RANSAC records (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     return MIM_OK;
 }
 
@@ -1194,28 +1195,17 @@ mim_status mim_knn2_sets_dev(mim_ctx* c, int32_t query_set, int32_t train_set, i
 // sets go through the float kernel on their f32 rows (no prep is needed or flushed).  With the lock held.
 static mim_status knn_topk_locked(mim_ctx* c, const mim_problem* problems, int n, int k, int32_t* idx_dev,
                                   float* dist_dev) {
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     if (k < 1 || k > MIM_KNN_MAX_K) return fail(c, MIM_EINVAL, "knn: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
     if (n < 0 || (n > 0 && !problems)) return fail(c, MIM_EINVAL, "knn: bad arguments");
     if (n == 0) return MIM_OK;
     mim_status s = device_limits(c);
     if (s != MIM_OK) return s;
-    std::vector<KnnSchedProblem> in(n);
-    long long rows = 0;
-    int max_nq = 0;
-    for (int i = 0; i < n; ++i) {
-        const int qs = problems[i].query_set, ts = problems[i].train_set;
-        s = check_problem_sets(c, i, qs, ts, false);
-        if (s != MIM_OK) return s;
-        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
-        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
-        in[i].fdim = Q.bin_pad ? 0 : Q.fdim ? Q.fdim : kDim;  // 128-D sets: the float work list at dim 128
-        rows += Q.d.n;
-        max_nq = std::max(max_nq, Q.d.n);
-    }
-    if (rows > 0 && (!idx_dev || !dist_dev)) return fail(c, MIM_EINVAL, "knn: null output");
+    ProblemList L;
+    s = problem_list(c, problems, n, false, false, L);  // 128-D sets: the float work list at dim 128
+    if (s != MIM_OK) return s;
+    const std::vector<KnnSchedProblem>& in = L.in;
+    if (L.qoff[n] > 0 && (!idx_dev || !dist_dev)) return fail(c, MIM_EINVAL, "knn: null output");
     KnnSchedule S;
     S.slots.assign(n, KnnSchedSlot{});
     knn_hamming_plan(in, c->n_cu, S);
@@ -1233,46 +1223,34 @@ static mim_status knn_topk_locked(mim_ctx* c, const mim_problem* problems, int n
     std::vector<TopkHamWork> ham;
     ham.reserve(S.ham.size());
     for (const HamPiece& hp : S.ham) {
-        const SetRec &Q = c->sets[problems[hp.problem].query_set], &T = c->sets[problems[hp.problem].train_set];
-        ham.push_back(TopkHamWork{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag),
+        const HamFields f = ham_fields(c, problems[hp.problem]);
+        ham.push_back(TopkHamWork{f.q, f.t,
                                   parts + Lo.part_off[hp.problem] + (long long)hp.split * S.slots[hp.problem].q_pad * k,
-                                  Q.d.n, hp.q0, hp.r0, hp.r1, Q.bin_pad / 4, 0});
+                                  f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
     }
     std::vector<TopkFltWork> flt;
     flt.reserve(S.flt.size());
     for (const FltPiece& fp : S.flt) {
-        const SetRec &Q = c->sets[problems[fp.problem].query_set], &T = c->sets[problems[fp.problem].train_set];
-        const int dim = Q.fdim ? Q.fdim : kDim, dp = Q.fdim ? Q.fpad : kDim;
-        const bool vec = (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0;
-        flt.push_back(TopkFltWork{Q.d.f32, T.d.f32,
+        const FltFields f = flt_fields(c, problems[fp.problem]);
+        flt.push_back(TopkFltWork{f.q, f.t,
                                   parts + Lo.part_off[fp.problem] + (long long)fp.split * S.slots[fp.problem].q_pad * k,
-                                  Q.d.n, fp.q0, fp.r0, fp.r1, dim, dp, T.d.n, vec ? 1 : 0});
+                                  f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec});
     }
     if (!ham.empty()) HIPCHK(c, c->topk_ham_works.ensure(sizeof(TopkHamWork) * ham.size()));
     if (!flt.empty()) HIPCHK(c, c->topk_flt_works.ensure(sizeof(TopkFltWork) * flt.size()));
     // the device tables are rewritten in stream order (after the previous call's kernels)
-    const size_t pb = sizeof(TopkProb) * probs.size(), hb = sizeof(TopkHamWork) * ham.size(),
-                 fb = sizeof(TopkFltWork) * flt.size();
-    char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + hb + fb, &st));
-    memcpy(st, probs.data(), pb);
-    HIPCHK(c, hipMemcpyAsync(c->topk_probs.p, st, pb, hipMemcpyHostToDevice, c->stream));
-    if (hb) {
-        memcpy(st + pb, ham.data(), hb);
-        HIPCHK(c, hipMemcpyAsync(c->topk_ham_works.p, st + pb, hb, hipMemcpyHostToDevice, c->stream));
-    }
-    if (fb) {
-        memcpy(st + pb + hb, flt.data(), fb);
-        HIPCHK(c, hipMemcpyAsync(c->topk_flt_works.p, st + pb + hb, fb, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, c->stage.release_after(c->stream));
+    StageWriter up(c->stage, vec_bytes(probs) + vec_bytes(ham) + vec_bytes(flt), c->stream);
+    up.put(c->topk_probs, probs);
+    up.put(c->topk_ham_works, ham);
+    up.put(c->topk_flt_works, flt);
+    HIPCHK(c, up.done());
     c->cur = c->stream;
     ev_mark(c, "begin");
     launch_knn_topk_hamming(c->topk_ham_works.as<TopkHamWork>(), (int)ham.size(), k, c->cur);
     launch_knn_topk_float(c->topk_flt_works.as<TopkFltWork>(), (int)flt.size(), k, c->cur);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "knn");
-    launch_knn_topk_merge(c->topk_probs.as<TopkProb>(), n, max_nq, k, c->cur);
+    launch_knn_topk_merge(c->topk_probs.as<TopkProb>(), n, L.max_nq, k, c->cur);
     HIPCHK(c, hipGetLastError());
     ev_mark(c, "ratio");
     return MIM_OK;
@@ -1295,59 +1273,38 @@ mim_status mim_knn_sets_dev(mim_ctx* c, int32_t query_set, int32_t train_set, in
     return knn_topk_locked(c, &pr, 1, k, idx_dev, dist_dev);
 }
 
-// the host-buffer forms: private sets appended after the user's sets and removed afterwards (as
-// mim_knn2_hamming; no prep is flushed on this path, so their storage always goes back to the arena)
-static mim_status knn_topk_host(mim_ctx* c, int nq, int k, int32_t* idx, float* dist,
-                                const std::function<mim_status(bool, int32_t*)>& create) {
-    const size_t base = c->sets.size();
-    const Arena::Mark mark = c->arena.pos();
-    auto run = [&]() -> mim_status {
-        int32_t sq, st;
-        mim_status s = create(true, &sq);
-        if (s != MIM_OK) return s;
-        s = create(false, &st);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * k * nq));
-        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * k * nq));
-        const mim_problem pr{sq, st};
-        s = knn_topk_locked(c, &pr, 1, k, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>());
-        if (s != MIM_OK) return s;
-        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * k * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * k * nq, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return MIM_OK;
-    };
-    const mim_status s = run();
-    ev_collect(c);
-    c->sets.resize(base);
-    c->arena.seek(mark);
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
-    return s;
+// body of the top-k host-buffer entries (no prep is flushed on this path)
+static mim_status knn_topk_host_body(mim_ctx* c, const mim_problem& pr, int nq, int k, int32_t* idx, float* dist) {
+    HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * k * nq));
+    HIPCHK(c, c->knn_dist.ensure(sizeof(float) * k * nq));
+    const mim_status s = knn_topk_locked(c, &pr, 1, k, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>());
+    if (s != MIM_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * k * nq, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * k * nq, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MIM_OK;
 }
 
 mim_status mim_knn_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim, int32_t k,
                       int32_t* idx, float* dist) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
-        return fail(c, MIM_EINVAL, "knn_l2: bad arguments");
+    if (check_host_pair(c, "knn_l2", q, nq, t, nt, nq <= 0 || (idx && dist)) != MIM_OK) return MIM_EINVAL;
     if (dim < 1 || dim > kFltMaxDim) return fail(c, MIM_EINVAL, "knn_l2: dim must be 1..%d (got %d)", kFltMaxDim, dim);
     if (k < 1 || k > MIM_KNN_MAX_K) return fail(c, MIM_EINVAL, "knn_l2: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
     if (nq == 0) return MIM_OK;  // knnMatch on an empty query returns no rows
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
-    return knn_topk_host(c, nq, k, idx, dist, [&](bool query, int32_t* id) {
-        return set_create_f32_locked(c, query ? q : t, (int64_t)4 * dim, kp0.data(), query ? nq : nt, dim, 0, id);
-    });
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_f32_locked(c, q, (int64_t)4 * dim, kp0.data(), nq, dim, 0, id); },
+        [&](int32_t* id) { return set_create_f32_locked(c, t, (int64_t)4 * dim, kp0.data(), nt, dim, 0, id); },
+        [&](const mim_problem& pr) { return knn_topk_host_body(c, pr, nq, k, idx, dist); });
 }
 
 mim_status mim_knn_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
                            int32_t k, int32_t* idx, float* dist) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
-        return fail(c, MIM_EINVAL, "knn_hamming: bad arguments");
+    if (check_host_pair(c, "knn_hamming", q, nq, t, nt, nq <= 0 || (idx && dist)) != MIM_OK) return MIM_EINVAL;
     if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "knn_hamming: width must be 1..64 bytes (got %d)", width);
     if (k < 1 || k > MIM_KNN_MAX_K)
         return fail(c, MIM_EINVAL, "knn_hamming: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
@@ -1355,9 +1312,10 @@ mim_status mim_knn_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> kp0((size_t)std::max(nq, nt) * 2, 0.f);
-    return knn_topk_host(c, nq, k, idx, dist, [&](bool query, int32_t* id) {
-        return set_create_bin_locked(c, query ? q : t, width, kp0.data(), query ? nq : nt, width, 0, id);
-    });
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, id); },
+        [&](int32_t* id) { return set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, id); },
+        [&](const mim_problem& pr) { return knn_topk_host_body(c, pr, nq, k, idx, dist); });
 }
 
 }  // extern "C"
@@ -1392,9 +1350,7 @@ static void radius_launch(mim_ctx* c, const RadArgs& a, bool fill) {
 // both lists, and the sets' integrality flags decide on the device which kernel's blocks do its pairs.
 static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, int n, float r, int64_t* offsets_dev,
                                       int64_t* total) {
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     c->rad.valid = false;
     if (!total || n < 0 || (n > 0 && !problems)) return fail(c, MIM_EINVAL, "radius: bad arguments");
     *total = 0;
@@ -1404,20 +1360,15 @@ static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, i
     if (s != MIM_OK) return s;
     s = device_limits(c);
     if (s != MIM_OK) return s;
-    std::vector<KnnSchedProblem> in(n), in8(n);
-    std::vector<long long> qoff(n + 1, 0);
+    ProblemList L;
+    s = problem_list(c, problems, n, false, false, L);
+    if (s != MIM_OK) return s;
+    const std::vector<KnnSchedProblem>& in = L.in;
+    const std::vector<long long>& qoff = L.qoff;
+    std::vector<KnnSchedProblem> in8 = in;  // the i8 schedule's view: the 128-D problems, every other out of it
     for (int i = 0; i < n; ++i) {
-        const int qs = problems[i].query_set, ts = problems[i].train_set;
-        s = check_problem_sets(c, i, qs, ts, false);
-        if (s != MIM_OK) return s;
-        const SetRec &Q = c->sets[qs], &T = c->sets[ts];
-        in[i] = KnnSchedProblem{Q.d.n, T.d.n, T.d.n_tiles, Q.bin_pad != 0};
-        in[i].fdim = Q.bin_pad ? 0 : Q.fdim ? Q.fdim : kDim;
-        in8[i] = in[i];
-        const bool sift = !Q.bin_pad && !Q.fdim;
-        in8[i].bin = !sift;  // out of the i8 schedule
+        in8[i].bin = !c->sets[problems[i].query_set].is_sift();
         in8[i].fdim = 0;
-        qoff[i + 1] = qoff[i] + Q.d.n;
     }
     const long long nqs = qoff[n];
     KnnSchedule S, S8;
@@ -1429,23 +1380,21 @@ static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, i
     std::vector<RadHamWork> ham;
     ham.reserve(S.ham.size());
     for (const HamPiece& hp : S.ham) {
-        const SetRec &Q = c->sets[problems[hp.problem].query_set], &T = c->sets[problems[hp.problem].train_set];
-        ham.push_back(RadHamWork{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag),
-                                 qoff[hp.problem], Q.d.n, hp.q0, hp.r0, hp.r1, Q.bin_pad / 4, 0});
+        const HamFields f = ham_fields(c, problems[hp.problem]);
+        ham.push_back(RadHamWork{f.q, f.t, qoff[hp.problem], f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
     }
     std::vector<RadFltWork> flt;
     flt.reserve(S.flt.size());
     for (const FltPiece& fp : S.flt) {
         const SetRec &Q = c->sets[problems[fp.problem].query_set], &T = c->sets[problems[fp.problem].train_set];
-        const int dim = Q.fdim ? Q.fdim : kDim, dp = Q.fdim ? Q.fpad : kDim;
-        const bool vec = (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0;
-        flt.push_back(RadFltWork{Q.d.f32, T.d.f32, Q.fdim ? nullptr : Q.d.flags, Q.fdim ? nullptr : T.d.flags,
-                                 qoff[fp.problem], Q.d.n, fp.q0, fp.r0, fp.r1, dim, dp, T.d.n, vec ? 1 : 0});
+        const FltFields f = flt_fields(c, problems[fp.problem]);
+        flt.push_back(RadFltWork{f.q, f.t, Q.is_sift() ? Q.d.flags : nullptr, Q.is_sift() ? T.d.flags : nullptr,
+                                 qoff[fp.problem], f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec});
     }
     std::vector<RadI8Prob> probs(n);
     for (int i = 0; i < n; ++i)
         probs[i] = RadI8Prob{c->sets[problems[i].query_set].d, c->sets[problems[i].train_set].d, qoff[i]};
-    const size_t wb = sizeof(KnnWork) * S8.works.size(), sb = sizeof(int) * S8.seg.size();
+    const size_t wb = vec_bytes(S8.works), sb = vec_bytes(S8.seg);
     HIPCHK(c, c->rad_counts.ensure(sizeof(int) * (nqs + 1)));
     HIPCHK(c, c->rad_cursor.ensure(sizeof(int) * (nqs + 1)));
     HIPCHK(c, c->rad_offsets.ensure(sizeof(long long) * (nqs + 1)));
@@ -1455,26 +1404,12 @@ static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, i
     if (!flt.empty()) HIPCHK(c, c->rad_flt_works.ensure(sizeof(RadFltWork) * flt.size()));
     if (wb) HIPCHK(c, c->rad_i8_works.ensure(wb + sb));
     // the device tables are rewritten in stream order (after the previous call's kernels)
-    const size_t pb = sizeof(RadI8Prob) * probs.size(), hb = sizeof(RadHamWork) * ham.size(),
-                 fb = sizeof(RadFltWork) * flt.size();
-    char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(pb + hb + fb + wb + sb + 16, &st));
-    size_t o = 0;
-    auto put = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        if (!bytes) return hipSuccess;
-        memcpy(st + o, src, bytes);
-        const hipError_t e = hipMemcpyAsync(dst, st + o, bytes, hipMemcpyHostToDevice, c->stream);
-        o += bytes;
-        return e;
-    };
-    HIPCHK(c, put(c->rad_probs.p, probs.data(), pb));
-    HIPCHK(c, put(c->rad_ham_works.p, ham.data(), hb));
-    HIPCHK(c, put(c->rad_flt_works.p, flt.data(), fb));
-    if (wb) {
-        HIPCHK(c, put(c->rad_i8_works.p, S8.works.data(), wb));
-        HIPCHK(c, put(static_cast<char*>(c->rad_i8_works.p) + wb, S8.seg.data(), sb));
-    }
-    HIPCHK(c, c->stage.release_after(c->stream));
+    StageWriter up(c->stage, vec_bytes(probs) + vec_bytes(ham) + vec_bytes(flt) + wb + sb, c->stream);
+    up.put(c->rad_probs, probs);
+    up.put(c->rad_ham_works, ham);
+    up.put(c->rad_flt_works, flt);
+    if (wb) up.put(c->rad_i8_works.p, S8.works.data(), wb, S8.seg.data(), sb);
+    HIPCHK(c, up.done());
     HIPCHK(c, hipMemsetAsync(c->rad_counts.p, 0, sizeof(int) * (nqs + 1), c->stream));
     c->rad.problems.assign(problems, problems + n);
     c->rad.r = r;
@@ -1506,9 +1441,7 @@ static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, i
 }
 
 static mim_status radius_fill_locked(mim_ctx* c, int32_t* idx_dev, float* dist_dev, int64_t cap) {
-    c->last_n = 0;
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     if (!c->rad.valid) return fail(c, MIM_EINVAL, "radius_fill: no mim_radius_count call to fill");
     if (c->rad.gen != c->sets_gen)
         return fail(c, MIM_EINVAL, "radius_fill: sets were cleared or truncated since the mim_radius_count call");
@@ -1534,59 +1467,26 @@ static mim_status radius_fill_locked(mim_ctx* c, int32_t* idx_dev, float* dist_d
     return MIM_OK;
 }
 
-// the host-buffer forms: private sets appended after the user's sets and removed afterwards.  The 128-D form
-// flushes its sets' prep, whose flags block comes from the arena after their storage: everything goes back
-// unless sets of the user's were still waiting for their prep and share that block (as mim_knn2_hamming).
-static mim_status radius_host(mim_ctx* c, int nq, float r, int64_t* offsets, int32_t* idx, float* dist, int64_t cap,
-                              const std::function<mim_status(bool, int32_t*)>& create) {
-    const size_t base = c->sets.size();
-    const Arena::Mark mark = c->arena.pos();
-    const bool reclaim = c->pend.empty();
-    auto run = [&]() -> mim_status {
-        int32_t sq, st;
-        mim_status s = create(true, &sq);
-        if (s != MIM_OK) return s;
-        s = create(false, &st);
-        if (s != MIM_OK) return s;
-        const mim_problem pr{sq, st};
-        int64_t total = 0;
-        s = radius_count_locked(c, &pr, 1, r, nullptr, &total);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, hipMemcpyAsync(offsets, c->rad_offsets.p, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!idx) return MIM_OK;  // offsets only
-        if (total > cap) return fail(c, MIM_ERANGE, "radius: %lld matches, room for %lld", (long long)total, (long long)cap);
-        if (total == 0) return MIM_OK;
-        HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * total));
-        HIPCHK(c, c->knn_dist.ensure(sizeof(float) * total));
-        s = radius_fill_locked(c, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>(), total);
-        if (s != MIM_OK) return s;
-        HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return MIM_OK;
-    };
-    const mim_status s = run();
-    ev_collect(c);
-    // the private sets go, with their pending preps (a failure before the flush) and the flush that covered them alone
-    size_t m = 0;
-    for (size_t j = 0; j < c->pend.size(); ++j)
-        if (c->pend_set[j] < (int)base) {
-            c->pend[m] = c->pend[j];
-            c->pend_set[m++] = c->pend_set[j];
-        }
-    c->pend.resize(m);
-    c->pend_set.resize(m);
-    c->flushes.erase(std::remove_if(c->flushes.begin(), c->flushes.end(),
-                                    [base](const std::pair<int, Arena::Mark>& f) { return f.first >= (int)base; }),
-                     c->flushes.end());
-    c->sets.resize(base);
-    if (reclaim) c->arena.seek(mark);
-    c->rad.valid = false;  // its sets are gone
-    c->last_n = 0;
-    c->last_gen = -1;
-    c->last_fh = false;
-    return s;
+// body of the radius host-buffer entries: the count and its offsets, then (idx != null) the fill.  The 128-D
+// form flushes its sets' prep, whose flags block comes from the arena after their storage.
+static mim_status radius_host_body(mim_ctx* c, const mim_problem& pr, int nq, float r, int64_t* offsets, int32_t* idx,
+                                   float* dist, int64_t cap) {
+    int64_t total = 0;
+    mim_status s = radius_count_locked(c, &pr, 1, r, nullptr, &total);
+    if (s != MIM_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(offsets, c->rad_offsets.p, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!idx) return MIM_OK;  // offsets only
+    if (total > cap) return fail(c, MIM_ERANGE, "radius: %lld matches, room for %lld", (long long)total, (long long)cap);
+    if (total == 0) return MIM_OK;
+    HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * total));
+    HIPCHK(c, c->knn_dist.ensure(sizeof(float) * total));
+    s = radius_fill_locked(c, c->knn_idx.as<int32_t>(), c->knn_dist.as<float>(), total);
+    if (s != MIM_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(idx, c->knn_idx.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist, c->knn_dist.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MIM_OK;
 }
 
 extern "C" {
@@ -1609,8 +1509,8 @@ mim_status mim_radius_fill_dev(mim_ctx* c, int32_t* idx_dev, float* dist_dev, in
 mim_status mim_radius_l2(mim_ctx* c, const float* q, int32_t nq, const float* t, int32_t nt, int32_t dim,
                          float max_distance, int64_t* offsets, int32_t* idx, float* dist, int64_t cap) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || !offsets || (nq > 0 && !q) || (nt > 0 && !t) || (idx && !dist) || cap < 0)
-        return fail(c, MIM_EINVAL, "radius_l2: bad arguments");
+    if (check_host_pair(c, "radius_l2", q, nq, t, nt, offsets && (!idx || dist) && cap >= 0) != MIM_OK)
+        return MIM_EINVAL;
     if (dim < 1 || dim > kFltMaxDim) return fail(c, MIM_EINVAL, "radius_l2: dim must be 1..%d (got %d)", kFltMaxDim, dim);
     if (!radius_arg_ok(max_distance))
         return fail(c, MIM_EINVAL, "radius_l2: max_distance must be above FLT_EPSILON (got %g)", (double)max_distance);
@@ -1619,20 +1519,21 @@ mim_status mim_radius_l2(mim_ctx* c, const float* q, int32_t nq, const float* t,
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> kp0((size_t)std::max(std::max(nq, nt), 1) * 2, 0.f);
-    return radius_host(c, nq, max_distance, offsets, idx, dist, cap, [&](bool query, int32_t* id) {
-        const float* rows = query ? q : t;
-        const int n = query ? nq : nt;
+    auto make = [&](const float* rows, int n, int32_t* id) {
         // dim 128: the 128-D path, so that integer rows take the MFMA kernel (the same bits either way)
         if (dim == kDim) return set_create_locked(c, rows ? rows : kp0.data(), kp0.data(), n, dim, 0, id);
         return set_create_f32_locked(c, rows, (int64_t)4 * dim, kp0.data(), n, dim, 0, id);
-    });
+    };
+    return with_private_sets(
+        c, [&](int32_t* id) { return make(q, nq, id); }, [&](int32_t* id) { return make(t, nt, id); },
+        [&](const mim_problem& pr) { return radius_host_body(c, pr, nq, max_distance, offsets, idx, dist, cap); });
 }
 
 mim_status mim_radius_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t width,
                               float max_distance, int64_t* offsets, int32_t* idx, float* dist, int64_t cap) {
     if (!c) return MIM_EINVAL;
-    if (nq < 0 || nt < 0 || !offsets || (nq > 0 && !q) || (nt > 0 && !t) || (idx && !dist) || cap < 0)
-        return fail(c, MIM_EINVAL, "radius_hamming: bad arguments");
+    if (check_host_pair(c, "radius_hamming", q, nq, t, nt, offsets && (!idx || dist) && cap >= 0) != MIM_OK)
+        return MIM_EINVAL;
     if (width < 1 || width > 64) return fail(c, MIM_EINVAL, "radius_hamming: width must be 1..64 bytes (got %d)", width);
     if (!radius_arg_ok(max_distance))
         return fail(c, MIM_EINVAL, "radius_hamming: max_distance must be above FLT_EPSILON (got %g)", (double)max_distance);
@@ -1641,9 +1542,10 @@ mim_status mim_radius_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const ui
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<float> kp0((size_t)std::max(std::max(nq, nt), 1) * 2, 0.f);
-    return radius_host(c, nq, max_distance, offsets, idx, dist, cap, [&](bool query, int32_t* id) {
-        return set_create_bin_locked(c, query ? q : t, width, kp0.data(), query ? nq : nt, width, 0, id);
-    });
+    return with_private_sets(
+        c, [&](int32_t* id) { return set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, id); },
+        [&](int32_t* id) { return set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, id); },
+        [&](const mim_problem& pr) { return radius_host_body(c, pr, nq, max_distance, offsets, idx, dist, cap); });
 }
 
 void mim_default_box_params(mim_box_params* p) {
@@ -2193,9 +2095,7 @@ mim_status mim_match_cross_sets(mim_ctx* c, int32_t query_set, int32_t train_set
     HIPCHK(c, hipSetDevice(c->device));
     mim_problem pr{query_set, train_set};
     mim_status s = build_tables(c, &pr, 1, 1, MIM_FILTER_CROSS);
-    c->last_n = 0;  // no RANSAC records: the previous batch's are invalidated (mim.h)
-    c->last_gen = -1;
-    c->last_fh = false;
+    invalidate_batch(c);
     if (s != MIM_OK) return s;
     const int nq = c->h_probs[0].q.n;
     HIPCHK(c, c->knn_idx.ensure(sizeof(int32_t) * std::max(nq, 1)));
@@ -2282,12 +2182,9 @@ mim_status mim_batch_inlier_points(mim_ctx* c, const float* scales, float* out_x
     const size_t tb = sizeof(long long) * (n + 1) + (scales ? sizeof(float) * n : 0);
     HIPCHK(c, c->inl_tab.ensure(tb));
     HIPCHK(c, c->inl_out.ensure(sizeof(float2) * total));
-    char* st = nullptr;
-    HIPCHK(c, c->stage.acquire(tb, &st));
-    memcpy(st, offsets, sizeof(long long) * (n + 1));
-    if (scales) memcpy(st + sizeof(long long) * (n + 1), scales, sizeof(float) * n);
-    HIPCHK(c, hipMemcpyAsync(c->inl_tab.p, st, tb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, c->stage.release_after(c->stream));
+    StageWriter up(c->stage, tb, c->stream);
+    up.put(c->inl_tab.p, offsets, sizeof(long long) * (n + 1), scales, scales ? sizeof(float) * n : 0);
+    HIPCHK(c, up.done());
     const long long* offs = c->inl_tab.as<long long>();
     launch_inlier_gather(c->probs.as<ProbDev>(), n, c->results.as<mim_result>(), c->good_t.as<int32_t>(),
                          c->masks.as<uint8_t>(), offs,
