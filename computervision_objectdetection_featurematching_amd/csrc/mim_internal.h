@@ -245,6 +245,10 @@ struct RansacBufs {
     long long stream_len;
     float4* inl;              // [good_off + k] compressed inliers for the refit (scratch)
     uint4* tiles;             // [good_off / 32 + tile][2][64] f16 MFMA operand tiles of the points
+    float4* tbox;             // [good_off / 32 + tile] (cx, cy, rx, ry): box of the tile's source points (scaled)
+    int* perm;                // [2 * good_off ..][2][n] scratch of the tiles' order (arrival order, row -> point)
+    int* surv;                // [it_off + k] iterations of the chunk whose capped upper bound beats the bar
+    int* nsurv;               // [problem] how many are listed
     int* err;                 // device error word (bit0: RNG stream exhausted)
     // Sampler stream: the getSubset replay of chunk c+1 runs on s2 concurrently with the bound /
     // candidate / exact / replay kernels of chunk c (null: everything on the caller's stream)

@@ -2594,6 +2594,7 @@ constexpr double kOutScale = 0x1p30;
 #define MIM_BOUND_WAVES 4
 #endif
 constexpr int kBoundThreads = 64 * MIM_BOUND_WAVES;  // iterations per MFMA bound block (64 per wave)
+constexpr int kSurvBlocks = 4;  // blocks per problem of the survivor-list bound (grid-stride over the list)
 constexpr int kTileChunk = MIM_BOUND_CHUNK;  // 32-point tiles per LDS stage of the MFMA bound kernel (2 x 16 KiB)
 
 // clamp to [0, 1]: folds into the producing instruction's clamp bit (no NaN reaches it here)
@@ -2618,38 +2619,72 @@ __device__ __forceinline__ void split_f16(double a, _Float16& hi, _Float16& lo) 
 
 // Point tiles of every active problem, once per batch: scales, then per 32-point tile the A-operand
 // fragments of lane l (row l & 31, k = 8 (l >> 5) .. + 7) for ax and ay.  Rows past n are zero.
+// Only the bound kernels read the tiles and both bounds are counts, so the rows' order is free: the
+// points are laid out so that consecutive tiles are compact in (x, y) of the source point, which the
+// capped bound (ransac_bound_mfma_kernel, kBoundCap) needs to be selective.  Order: ~sqrt(tiles)
+// x-strips of about equal count (quantiles of a kTileXBins histogram), inside a strip by kTileYBins
+// uniform y bins, ascending and descending in turn (a snake: a tile that straddles two strips stays at
+// one end of y); a counting sort over (strip, y bin), ties by point index so that the order does not
+// depend on the atomics' timing.  tbox[tile] = (cx, cy, rx, ry): a box around the real rows of the
+// tile in the scaled coordinates x' = sa x (exact), half extents rounded outward.  The order affects
+// the capped bound's tightness only; the boxes are taken from the rows actually in the tile.
+constexpr int kTileXBins = 1024;
+constexpr int kTileYBins = 64;
+constexpr int kTileStripsMax = 32;
+constexpr int kTileKeys = kTileStripsMax * kTileYBins;
+// Problems below this many points keep the match order and take the full bound alone (no capped stage):
+// their tile loop is at most 4 tiles beside the fp64 hypothesis of every lane, which a second stage
+// would repeat for the survivors, and 1-4 tiles cannot be made compact (measured: DESIGN.md §10 item 2)
+constexpr int kCapMinN = 128;
+
 __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restrict__ st,
                                                            const ProbDev* __restrict__ probs,
                                                            const float4* __restrict__ pts,
-                                                           uint4* __restrict__ tiles) {
-    __shared__ float red[3][4];
+                                                           uint4* __restrict__ tiles, float4* __restrict__ tbox,
+                                                           int* __restrict__ perm, int* __restrict__ nsurv) {
+    __shared__ float red[7][4];
+    __shared__ int start[kTileKeys + 1], cur[kTileKeys];
+    __shared__ unsigned char strip_of[kTileXBins];
+    __shared__ int wred[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     RansacState* Sp = st + p;
+    if (tid == 0) nsurv[p] = 0;  // the survivor list of the one chunk after the first starts empty
     if (!Sp->active || Sp->done) return;
     const int n = Sp->n;
     const long long go = probs[p].good_off;  // multiple of 32 (knn_layout_offsets)
     const float4* __restrict__ P = pts + go;
     float mxy = 0.f, muv = 0.f, ms = 0.f;
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
     for (int i = tid; i < n; i += 256) {
         const float4 q = P[i];
         mxy = fmaxf(mxy, fmaxf(fabsf(q.x), fabsf(q.y)));
         muv = fmaxf(muv, fmaxf(fabsf(q.z), fabsf(q.w)));
         ms = fmaxf(ms, fabsf(q.x) + fabsf(q.y) + fabsf(q.z) + fabsf(q.w));
+        x0 = fminf(x0, q.x); x1 = fmaxf(x1, q.x);
+        y0 = fminf(y0, q.y); y1 = fmaxf(y1, q.y);
     }
     for (int off = 32; off >= 1; off >>= 1) {
         mxy = fmaxf(mxy, __shfl_xor(mxy, off));
         muv = fmaxf(muv, __shfl_xor(muv, off));
         ms = fmaxf(ms, __shfl_xor(ms, off));
+        x0 = fminf(x0, __shfl_xor(x0, off)); x1 = fmaxf(x1, __shfl_xor(x1, off));
+        y0 = fminf(y0, __shfl_xor(y0, off)); y1 = fmaxf(y1, __shfl_xor(y1, off));
     }
     if ((tid & 63) == 0) {
         red[0][tid >> 6] = mxy;
         red[1][tid >> 6] = muv;
         red[2][tid >> 6] = ms;
+        red[3][tid >> 6] = x0; red[4][tid >> 6] = x1;
+        red[5][tid >> 6] = y0; red[6][tid >> 6] = y1;
     }
     __syncthreads();
     mxy = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
     muv = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
     ms = fmaxf(fmaxf(red[2][0], red[2][1]), fmaxf(red[2][2], red[2][3]));
+    x0 = fminf(fminf(red[3][0], red[3][1]), fminf(red[3][2], red[3][3]));
+    x1 = fmaxf(fmaxf(red[4][0], red[4][1]), fmaxf(red[4][2], red[4][3]));
+    y0 = fminf(fminf(red[5][0], red[5][1]), fminf(red[5][2], red[5][3]));
+    y1 = fmaxf(fmaxf(red[6][0], red[6][1]), fmaxf(red[6][2], red[6][3]));
     int ea = 0, eb = 0;
     (void)frexpf(mxy, &ea);  // mxy < 2^ea
     (void)frexpf(muv, &eb);
@@ -2661,12 +2696,76 @@ __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restri
     }
     uint4* __restrict__ T = tiles + (go >> 5) * 128;
     const int nt = (n + 31) >> 5;
+    // ---- the source-local order: key = (x-strip, snaked y bin), counting sort ----
+    int ns = 1;
+    while (ns < kTileStripsMax && (2 * ns + 1) * (2 * ns + 1) <= 4 * nt) ++ns;  // sqrt(tiles) strips, rounded
+    const float invx = x1 > x0 ? (float)kTileXBins / (x1 - x0) : 0.f;
+    const float invy = y1 > y0 ? (float)kTileYBins / (y1 - y0) : 0.f;
+    // (the float -> int conversion saturates and maps NaN to 0; clamped into the table either way)
+    auto xbin = [&](float x) { return max(0, min(kTileXBins - 1, (int)((x - x0) * invx))); };
+    auto key = [&](const float4 q) {
+        const int sx = strip_of[xbin(q.x)];
+        const int yb = max(0, min(kTileYBins - 1, (int)((q.y - y0) * invy)));
+        return sx * kTileYBins + ((sx & 1) ? kTileYBins - 1 - yb : yb);
+    };
+    const bool local = n >= kCapMinN;  // uniform over the block
+    int* __restrict__ A = perm + 2 * go;  // the key's segment in arrival order, then B: row -> point
+    int* __restrict__ B = A + n;
+    if (local) {
+        for (int k = tid; k < kTileXBins; k += 256) start[k] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) atomicAdd(&start[xbin(P[i].x)], 1);
+        __syncthreads();
+        {  // strip of every x bin: where the middle of the bin's points falls among ns equal counts
+            constexpr int kPer = kTileXBins / 256;
+            int c[kPer], sum = 0;
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) sum += c[k] = start[tid * kPer + k];
+            int total;
+            int base = block_excl_sum(sum, wred, total);
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                strip_of[tid * kPer + k] = (unsigned char)min(ns - 1, (int)(((long long)base * 2 + c[k]) * ns / (2LL * n)));
+                base += c[k];
+            }
+        }
+        __syncthreads();
+        for (int k = tid; k < kTileKeys; k += 256) cur[k] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) atomicAdd(&cur[key(P[i])], 1);
+        __syncthreads();
+        {
+            constexpr int kPer = kTileKeys / 256;
+            int c[kPer], sum = 0;
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) sum += c[k] = cur[tid * kPer + k];
+            int total;
+            int base = block_excl_sum(sum, wred, total);
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                start[tid * kPer + k] = cur[tid * kPer + k] = base;
+                base += c[k];
+            }
+            if (tid == 255) start[kTileKeys] = base;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) A[atomicAdd(&cur[key(P[i])], 1)] = i;
+        __syncthreads();
+    }
     // the fragments carry kPointScale = 2^15 (|x'| < 1, so every entry stays below 2^15 in f16)
     const _Float16 one = (_Float16)kPointScale;
-    for (int i = tid; i < nt * 32; i += 256) {
+    for (int j = tid; j < nt * 32; j += 256) {
         h8v lo = {}, axh = {}, ayh = {};
-        if (i < n) {
+        int r = j;  // zero rows stay at the end
+        if (j < n) {
+            const int i = local ? A[j] : j;
             const float4 q = P[i];
+            if (local) {
+                const int k = key(q), s0 = start[k], s1 = start[k + 1];
+                r = s0;
+                for (int m = s0; m < s1; ++m) r += A[m] < i;  // rank inside the key's segment by point index
+            }
+            B[r] = i;
             const float x = q.x * sa, y = q.y * sa, u = q.z * sb, v = q.w * sb;
             const float xk = x * kPointScale, yk = y * kPointScale, uk = u * kPointScale, vk = v * kPointScale;
             _Float16 a, b;
@@ -2680,12 +2779,37 @@ __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restri
             split_f16(v * yk, a, b); ayh[3] = a; ayh[4] = b; ayh[5] = a;
             split_f16(vk, a, b); ayh[6] = a; ayh[7] = b;
         }
-        uint4* t = T + (i >> 5) * 128;
-        const int r = i & 31;
+        uint4* t = T + (r >> 5) * 128;
+        r &= 31;
         t[r] = __builtin_bit_cast(uint4, lo);        // ax, lanes 0-31
         t[32 + r] = __builtin_bit_cast(uint4, axh);  // ax, lanes 32-63
         t[64 + r] = __builtin_bit_cast(uint4, lo);   // ay, lanes 0-31
         t[96 + r] = __builtin_bit_cast(uint4, ayh);  // ay, lanes 32-63
+    }
+    __syncthreads();
+    // boxes of the tiles' real rows, 32 lanes per tile (x' = sa x is exact: sa is a power of two)
+    float4* __restrict__ TB = tbox + (go >> 5);
+    for (int tb = 0; tb < nt; tb += 8) {
+        const int t = tb + (tid >> 5), row = t * 32 + (tid & 31);
+        float bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
+        if (row < n) {
+            const float4 q = P[B[row]];
+            bx0 = bx1 = q.x * sa;
+            by0 = by1 = q.y * sa;
+        }
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+            bx0 = fminf(bx0, __shfl_xor(bx0, off)); bx1 = fmaxf(bx1, __shfl_xor(bx1, off));
+            by0 = fminf(by0, __shfl_xor(by0, off)); by1 = fmaxf(by1, __shfl_xor(by1, off));
+        }
+        if (t < nt && (tid & 31) == 0) {
+            // the centre is any point of the box; the half extents cover both ends after their
+            // subtraction's rounding (2^-24 relative)
+            const float cx = 0.5f * (bx0 + bx1), cy = 0.5f * (by0 + by1);
+            const float rx = fmaxf(bx1 - cx, cx - bx0) * (1.f + 0x1p-22f);
+            const float ry = fmaxf(by1 - cy, cy - by0) * (1.f + 0x1p-22f);
+            TB[t] = make_float4(cx, cy, rx, ry);
+        }
     }
 }
 
@@ -2716,7 +2840,32 @@ __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restri
 // v_alignbit and a v_bcnt at the slow rate; hi = floor(sum + slack) - padded rows, slack bounding
 // the float sum's rounding.  The lower bound adds clamp(C_lo |W'| - K E_lo - (|X'| + |Y'|)), positive
 // only where the point is surely in, so lo = ceil(sum - slack) never exceeds the exact count.
-template <bool kLo>
+//
+// Capped form (kBoundCap; the chunks after the first, stage 1 of a cascade).  W = h6 x + h7 y + h8 is
+// affine in the source point alone, so over a tile whose real rows lie in the box (cx, cy, rx, ry)
+// (ransac_tiles_kernel: x' exact, extents rounded outward)
+//   |W_t| <= Wcap = |h6 cx + h7 cy + h8| + |h6| rx + |h7| ry     for every real row t of the tile,
+// and an inlier, |ex_t| + |ey_t| <= C |W_t| + 2 A in true scaled values, also has
+//   |ex| + |ey| <= C Wcap + 2 A + 2 kMfmaErr
+// in the MFMA outputs (each within kMfmaErr of the true value).  The cap is formed in fp32 from the
+// hypothesis rounded to float (3 x 2^-24, all factors <= 1) in four fmas on values <= 3 (4 x 3 x
+// 2^-24): below 1e-6 < 2^-19 absolute, which is added; E keeps the full form's (C + 2) kMfmaErr + 2 A.
+// So R = C (K Wcap) + (K (E + C 2^-19) + 1) per (tile, column block) and keep += clamp(R - |X'| - |Y'|)
+// per pair: two MFMAs and three VALU, no W product.  The same counting argument holds (R >= 3, the
+// same 1e-6 slack over three roundings; a zero row adds exactly 1), so hi1 = floor(sum + slack) -
+// padded rows >= the full form's test count >= the exact count: a valid upper bound, looser than hi.
+// Stage 1 writes (0, hi1) and lists the iteration as a survivor iff hi1 > bar = max(3, max_good, lo_max)
+// read from the state at launch: the earlier chunk's replay has finished on this stream, max_good and
+// lo_max only grow, and a chunk without lower bounds keeps the candidate rule's bar constant, so an
+// iteration that is not listed can never be a candidate (ransac_cand_kernel), whatever its hi.
+// Stage 2 (kList) is the full upper form over the survivor list, 256 entries per block in a grid-stride
+// loop; it overwrites the survivors' records with today's (0, hi).  The list holds a whole chunk
+// (it_off spacing), so no survivor is dropped; its order is the atomics' and does not matter.
+// A problem below kCapMinN points is left alone by stage 1, which marks its list length -1, and
+// stage 2's blocks then take its whole chunk in order: every iteration ends with a computed record.
+enum { kBoundUp = 0, kBoundLoUp = 1, kBoundCap = 2 };
+
+template <int kMode, bool kList>
 __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const RansacState* __restrict__ st,
                                                                 const ProbDev* __restrict__ probs,
                                                                 const float4* __restrict__ pts,
@@ -2724,7 +2873,13 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
                                                                 const uint32_t* __restrict__ stream,
                                                                 const uint4* __restrict__ tiles,
                                                                 int2* __restrict__ bounds, int c0, int c1, int bpp,
-                                                                float thr2, int n_probs) {
+                                                                float thr2, int n_probs,
+                                                                const float4* __restrict__ tbox,
+                                                                int* __restrict__ surv, int* __restrict__ nsurv,
+                                                                int list_all) {
+    constexpr bool kLo = kMode == kBoundLoUp;
+    constexpr bool kCap = kMode == kBoundCap;
+    static_assert(!(kList && kMode != kBoundUp), "the survivor list takes the full upper form");
     __shared__ uint4 lt[2][kTileChunk * 128];
     // XCD-aware order: blocks b and b + 8 share an XCD under round-robin dispatch (speed only), so
     // problem p's blocks are the ones with b % 8 == p % 8 and its point tiles are fetched into one
@@ -2733,11 +2888,26 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
     const int p = xcd + 8 * (j / bpp), kb = j % bpp;
     if (p >= n_probs) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int it = c0 + kb * kBoundThreads + tid;
     const RansacState S = st[p];
     if (!S.active || S.done) return;  // uniform over the block
-    if (c0 + kb * kBoundThreads >= min(c1, S.produced)) return;  // whole block idle
-    const bool act = it < c1 && it < S.produced;
+    if (kCap && !list_all && S.n < kCapMinN) {  // a small problem: the full bound alone, from stage 2's grid
+        if (kb == 0 && tid == 0) nsurv[p] = -1;
+        return;
+    }
+    const int n_list0 = kList ? nsurv[p] : 0;
+    const bool contig = kList && n_list0 < 0;  // the whole chunk in order instead of a list
+    const int n_list = contig ? max(0, min(c1, S.produced) - c0) : n_list0;
+    // list form: entries lk .. lk + 255 of the problem's survivor list, lk striding over the grid
+    for (int lk = kb * kBoundThreads; !kList || lk < n_list; lk += bpp * kBoundThreads) {
+    int it = c0 + kb * kBoundThreads + tid;
+    bool act;
+    if (kList) {
+        act = lk + tid < n_list;
+        it = !act ? c0 : contig ? c0 + lk + tid : surv[probs[p].it_off + lk + tid];
+    } else {
+        if (c0 + kb * kBoundThreads >= min(c1, S.produced)) return;  // whole block idle
+        act = it < c1 && it < S.produced;
+    }
     const long long o = probs[p].it_off + it;
     const long long go = probs[p].good_off;
     const float4* __restrict__ P = pts + go;
@@ -2826,8 +2996,20 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
     const h8v b1y = __builtin_bit_cast(h8v, lowh ? r2 : un);
     const h8v b1w = __builtin_bit_cast(h8v, lowh ? r3 : zero4);
     // in output units: K E + 1 (the band outside the upper test) and -K E_lo
-    const float EK = fmaf(E, (float)kOutScale, 1.f), ELK = -EL * (float)kOutScale;
+    // (capped form: with the cap's own fp32 rounding, 2^-19 in the scaled units, under C)
+    const float EK = fmaf(kCap ? (E + C * 0x1p-19f) * (1.f + 1e-6f) : E, (float)kOutScale, 1.f);
+    const float ELK = -EL * (float)kOutScale;
     const float Cp = __shfl_xor(C, 32), Ep = __shfl_xor(EK, 32);
+    // capped form: K (h6, h7, h8) of the two column blocks' hypotheses, as floats
+    float wa0 = 0.f, wb0 = 0.f, wc0 = 0.f, wa1 = 0.f, wb1 = 0.f, wc1 = 0.f;
+    if (kCap) {
+        const float wa = count ? (float)h[6] * (float)kOutScale : 0.f;
+        const float wb = count ? (float)h[7] * (float)kOutScale : 0.f;
+        const float wc = count ? (float)h[8] * (float)kOutScale : 0.f;
+        const float wap = __shfl_xor(wa, 32), wbp = __shfl_xor(wb, 32), wcp = __shfl_xor(wc, 32);
+        wa0 = lowh ? wa : wap; wb0 = lowh ? wb : wbp; wc0 = lowh ? wc : wcp;
+        wa1 = lowh ? wap : wa; wb1 = lowh ? wbp : wb; wc1 = lowh ? wcp : wc;
+    }
     const float C0 = lowh ? C : Cp, E0 = lowh ? EK : Ep, C1 = lowh ? Cp : C, E1 = lowh ? Ep : EK;
     float CL0 = 0.f, EL0 = 0.f, CL1 = 0.f, EL1 = 0.f;
     if (kLo) {
@@ -2836,6 +3018,7 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
     }
     const bool wave_counts = __any(count);
     const uint4* __restrict__ T = tiles + (go >> 5) * 128;
+    const float4* __restrict__ TB = tbox + (go >> 5);
     const int nt = (n + 31) >> 5;
     float keep0 = 0.f, keep1 = 0.f, in0 = 0.f, in1 = 0.f;  // float counts (see above)
     // point tiles through LDS by LDS-DMA in chunks of kTileChunk, double buffered: the next chunk's
@@ -2857,6 +3040,37 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
         const int tc = min(kTileChunk, nt - t0);
         if (t0 + kTileChunk < nt) stage(t0 + kTileChunk, buf ^ 1);
         if (wave_counts && MIM_PROBE_BOUND == 0) {
+          if (kCap) {  // |W'| capped over the tile's box: no W product
+            // the chunk's boxes (uniform: scalar loads) in one batch ahead of the tiles, so that no
+            // tile waits for its own; the tile loop is unrolled to keep them in scalar registers
+            float4 bx[kTileChunk];
+#pragma unroll
+            for (int t = 0; t < kTileChunk; ++t) bx[t] = TB[min(t0 + t, nt - 1)];
+            // (pinned here: the loads would otherwise sink into the tiles' conditional blocks)
+#pragma unroll
+            for (int t = 0; t < kTileChunk; ++t)
+                asm volatile("" : "+s"(bx[t].x), "+s"(bx[t].y), "+s"(bx[t].z), "+s"(bx[t].w));
+#pragma unroll
+            for (int t = 0; t < kTileChunk; ++t) {
+                if (t >= tc) break;
+                const h8v ax = __builtin_bit_cast(h8v, lt[buf][t * 128 + lane]);
+                const h8v ay = __builtin_bit_cast(h8v, lt[buf][t * 128 + 64 + lane]);
+                const f16acc zc = {};
+                const f16acc ex0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ax, b0x, zc, 0, 0, 0);
+                const f16acc ey0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b0y, zc, 0, 0, 0);
+                const f16acc ex1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ax, b1x, zc, 0, 0, 0);
+                const f16acc ey1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b1y, zc, 0, 0, 0);
+                const float R0 = fmaf(C0, fmaf(fabsf(wa0), bx[t].z, fmaf(fabsf(wb0), bx[t].w,
+                                          fabsf(fmaf(wa0, bx[t].x, fmaf(wb0, bx[t].y, wc0))))), E0);
+                const float R1 = fmaf(C1, fmaf(fabsf(wa1), bx[t].z, fmaf(fabsf(wb1), bx[t].w,
+                                          fabsf(fmaf(wa1, bx[t].x, fmaf(wb1, bx[t].y, wc1))))), E1);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    keep0 += clamp01((R0 - fabsf(ex0[r])) - fabsf(ey0[r]));
+                    keep1 += clamp01((R1 - fabsf(ex1[r])) - fabsf(ey1[r]));
+                }
+            }
+          } else
           for (int t = 0; t < tc; ++t) {
             const h8v ax = __builtin_bit_cast(h8v, lt[buf][t * 128 + lane]);
             const h8v ay = __builtin_bit_cast(h8v, lt[buf][t * 128 + 64 + lane]);
@@ -2906,6 +3120,18 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
         lo = min(hi, max(0, (int)ceil(ii - m2 * (ii + 1.0))));
     }
     if (act) bounds[o] = invalid ? make_int2(-1, -1) : (uncertain ? make_int2(0, n) : make_int2(lo, hi));
+    if (kCap) {  // stage 1: the countable iterations above the bar go on (wave-aggregated append)
+        const bool on = count && (list_all || hi > max(3, max(S.max_good, S.lo_max)));
+        const unsigned long long m = __ballot(on);
+        if (m) {
+            int base = 0;
+            if (lane == __ffsll((long long)m) - 1) base = atomicAdd(nsurv + p, __popcll(m));
+            base = __shfl(base, __ffsll((long long)m) - 1);
+            if (on) surv[probs[p].it_off + base + __popcll(m & ((1ull << lane) - 1))] = it;
+        }
+    }
+    if (!kList) break;
+    }
 }
 
 // exact count of one hypothesis (runKernel + computeError + findInliers, bit-exact)
@@ -4135,7 +4361,13 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
     if (const char* fc = getenv("MIM_FIRST_CHUNK")) first = std::max(1, atoi(fc));
     int c0 = 0, chunk = first;
     const float thr2 = (float)(prm.thresh * prm.thresh);
-    if (!exact_all) ransac_tiles_kernel<<<n_probs, 256, 0, s>>>(b.state, probs, pts, b.tiles);
+    if (!exact_all) ransac_tiles_kernel<<<n_probs, 256, 0, s>>>(b.state, probs, pts, b.tiles, b.tbox, b.perm, b.nsurv);
+    // chunks after the first: capped bound, then the full one for its survivors (MIM_BOUND_CAP=0: the
+    // full bound over every iteration; MIM_BOUND_CAP_ALL=1: test knob, every countable iteration survives)
+    const char* bce = getenv("MIM_BOUND_CAP");
+    const int bound_cap = (bce && bce[0] == '0') ? 0 : 1;
+    const char* bae = getenv("MIM_BOUND_CAP_ALL");
+    const int cap_all = (bae && bae[0] == '1') ? 1 : 0;
     // the getSubset replay on the sampler stream when there is one (not in the reference mode)
     const bool split = b.s2 && !exact_all;
     hipStream_t ss = split ? b.s2 : s;
@@ -4264,11 +4496,37 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
             }
         } else {
             if (c0 == 0)
-                ransac_bound_mfma_kernel<true><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
-                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs);
-            else
-                ransac_bound_mfma_kernel<false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
-                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs);
+                ransac_bound_mfma_kernel<kBoundLoUp, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
+                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
+                    b.surv, b.nsurv, 0);
+            else if (!bound_cap)
+                ransac_bound_mfma_kernel<kBoundUp, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
+                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
+                    b.surv, b.nsurv, 0);
+            else {
+                // stage 2's grid is fixed (the host does not know the counts): kSurvBlocks blocks per
+                // problem stride over its list; a block without entries ends after two loads
+                const int bppl = std::min(bppb, kSurvBlocks);
+                ransac_bound_mfma_kernel<kBoundCap, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
+                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
+                    b.surv, b.nsurv, cap_all);
+                ransac_bound_mfma_kernel<kBoundUp, true><<<8 * ((n_probs + 7) / 8) * bppl, kBoundThreads, 0, s>>>(
+                    b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppl, thr2, n_probs, b.tbox,
+                    b.surv, b.nsurv, 0);
+                if (getenv("MIM_DEBUG_NSURV")) {
+                    std::vector<int> h(n_probs);
+                    (void)hipMemcpyAsync(h.data(), b.nsurv, sizeof(int) * n_probs, hipMemcpyDeviceToHost, s);
+                    (void)hipStreamSynchronize(s);
+                    long long sum = 0; int mx = 0, small = 0;
+                    for (int i = 0; i < n_probs; ++i) {
+                        sum += std::max(h[i], 0);
+                        mx = std::max(mx, h[i]);
+                        small += h[i] < 0;
+                    }
+                    fprintf(stderr, "[mim] chunk [%d,%d): survivors mean %.1f max %d (%d small problems on the full bound alone)\n",
+                            c0, c1, (double)sum / n_probs, mx, small);
+                }
+            }
             mark(mark_ctx, "score", s);
             if (getenv("MIM_CHECK_BOUNDS")) {  // debug: every bracket against the exact count
                 unsigned long long* dst = nullptr;
