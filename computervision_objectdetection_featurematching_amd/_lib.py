@@ -30,6 +30,7 @@ EXPORTS = [
     "mim_batch_run_filter", "mim_match_cross_sets",
     "mim_knn_batch_dev", "mim_knn_sets_dev", "mim_knn_l2", "mim_knn_hamming",
     "mim_radius_count", "mim_radius_fill_dev", "mim_radius_l2", "mim_radius_hamming",
+    "mim_knn_collection_dev",
 ]
 
 
@@ -122,6 +123,7 @@ def load():
     L.mim_knn_sets_dev.argtypes = [vp, i32, i32, i32, vp, vp]
     L.mim_knn_l2.argtypes = [vp, f32p, i32, f32p, i32, i32, i32, i32p, f32p]
     L.mim_knn_hamming.argtypes = [vp, u8p, i32, u8p, i32, i32, i32, i32p, f32p]
+    L.mim_knn_collection_dev.argtypes = [vp, i32p, i32, i32p, i32, i32, vp, vp, vp]
     L.mim_radius_count.argtypes = [vp, C.POINTER(Problem), i32, C.c_float, vp, C.POINTER(C.c_int64)]
     L.mim_radius_fill_dev.argtypes = [vp, vp, vp, C.c_int64]
     L.mim_radius_l2.argtypes = [vp, f32p, i32, f32p, i32, i32, C.c_float, vp, i32p, f32p, C.c_int64]
@@ -168,7 +170,8 @@ def load():
                  "mim_group_scene_points", "mim_sift_scales_sets_image", "mim_cvt_bgr2gray_u8", "mim_set_create_bin",
                  "mim_knn2_hamming", "mim_set_create_f32", "mim_knn2_l2_f32", "mim_batch_run_filter",
                  "mim_match_cross_sets", "mim_knn_batch_dev", "mim_knn_sets_dev", "mim_knn_l2", "mim_knn_hamming",
-                 "mim_radius_count", "mim_radius_fill_dev", "mim_radius_l2", "mim_radius_hamming"):
+                 "mim_radius_count", "mim_radius_fill_dev", "mim_radius_l2", "mim_radius_hamming",
+                 "mim_knn_collection_dev"):
         getattr(L, name).restype = C.c_int32
     for name in ("mim_ctx_create", "mim_ctx_set_stream", "mim_synchronize", "mim_set_create", "mim_sets_create", "mim_sets_clear",
                  "mim_sets_truncate", "mim_knn2_l2", "mim_ratio_filter", "mim_find_homography", "mim_batch_run", "mim_batch_results",

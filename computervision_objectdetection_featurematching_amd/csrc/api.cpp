@@ -21,6 +21,7 @@
 
 #include "../../include/mim.h"
 #include "../../include/mim_detect.hpp"
+#include "knn_coll.h"
 #include "mim_internal.h"
 #include "radius.h"
 
@@ -231,6 +232,11 @@ struct mim_ctx {
     // top-k entries (mim_knn_batch_dev): partial lists, work items and the merge's problem table
     DevBuf topk_parts, topk_ham_works, topk_flt_works, topk_probs;
     int topk_splits = 0;  // the most train splits of a problem of the last such call
+    // train collections (mim_knn_collection_dev): one group's partial lists, the work items of its
+    // three distance kernels, the i8 kernel's pair records and the merge's tables
+    DevBuf coll_parts, coll_ham_works, coll_flt_works, coll_i8_probs, coll_i8_works, coll_tab, coll_queries;
+    int coll_groups = 0;     // image groups of the last such call
+    int coll_i8_splits = 0;  // the most train splits the i8 schedule gave a pair of it
     // radius matching (mim_radius_count / mim_radius_fill_dev): the call's arrays, the work items
     // of its three distance kernels, and what the last count call left for the fills that follow it
     DevBuf rad_counts, rad_cursor, rad_offsets, rad_meta, rad_keys, rad_scratch, rad_ham_works, rad_flt_works, rad_i8_works,
@@ -393,7 +399,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->prep_stage.destroy();
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
-                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->rad_counts, &c->rad_cursor, &c->rad_offsets, &c->rad_meta, &c->rad_keys, &c->rad_scratch, &c->rad_ham_works, &c->rad_flt_works, &c->rad_i8_works, &c->rad_probs, &c->rws.state, &c->rws.samples,
+                      &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->coll_parts, &c->coll_ham_works, &c->coll_flt_works, &c->coll_i8_probs, &c->coll_i8_works, &c->coll_tab, &c->coll_queries, &c->rad_counts, &c->rad_cursor, &c->rad_offsets, &c->rad_meta, &c->rad_keys, &c->rad_scratch, &c->rad_ham_works, &c->rad_flt_works, &c->rad_i8_works, &c->rad_probs, &c->rws.state, &c->rws.samples,
                       &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.tbox, &c->rws.perm, &c->rws.surv, &c->rws.nsurv, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -435,6 +441,8 @@ double mim_last_kernel_ms(mim_ctx* c, const char* name) {
     if (!c || !name) return -1;
     if (!strcmp(name, "knn_cross")) return c->knn_cross;  // nor this: how the last batch found the reverse neighbours
     if (!strcmp(name, "knn_topk_splits")) return c->topk_splits;  // nor this: the last top-k call's most train splits
+    if (!strcmp(name, "knn_coll_groups")) return c->coll_groups;  // nor these: the last collection call's image groups
+    if (!strcmp(name, "knn_coll_i8_splits")) return c->coll_i8_splits;  // and the most i8 train splits of a pair of it
     if (!strcmp(name, "radius_sort_cap")) return kRadSortCap;  // nor this: the longest list the radius sort keeps in LDS
     if (!strcmp(name, "knn_mode")) return c->knn_mode;  // not a time: the form the last batch's distance kernel ran in
     auto it = c->last_ms.find(name);
@@ -1234,7 +1242,7 @@ static mim_status knn_topk_locked(mim_ctx* c, const mim_problem* problems, int n
         const FltFields f = flt_fields(c, problems[fp.problem]);
         flt.push_back(TopkFltWork{f.q, f.t,
                                   parts + Lo.part_off[fp.problem] + (long long)fp.split * S.slots[fp.problem].q_pad * k,
-                                  f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec});
+                                  f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec, nullptr, nullptr});
     }
     if (!ham.empty()) HIPCHK(c, c->topk_ham_works.ensure(sizeof(TopkHamWork) * ham.size()));
     if (!flt.empty()) HIPCHK(c, c->topk_flt_works.ensure(sizeof(TopkFltWork) * flt.size()));
@@ -1316,6 +1324,191 @@ mim_status mim_knn_hamming(mim_ctx* c, const uint8_t* q, int32_t nq, const uint8
         c, [&](int32_t* id) { return set_create_bin_locked(c, q, width, kp0.data(), nq, width, 0, id); },
         [&](int32_t* id) { return set_create_bin_locked(c, t, width, kp0.data(), nt, width, 0, id); },
         [&](const mim_problem& pr) { return knn_topk_host_body(c, pr, nq, k, idx, dist); });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Train collections: every query set against the same images, one list per query row.
+// ---------------------------------------------------------------------------------------------
+// the byte budget of one image group's partial lists; MIM_COLL_PART_BYTES, read per call (tests force one
+// image per group)
+static long long coll_part_budget() {
+    long long b = 256LL << 20;
+    if (const char* e = getenv("MIM_COLL_PART_BYTES")) b = atoll(e);
+    return std::max<long long>(b, 1);
+}
+
+// One image group's plans, made on the host before anything of the call is enqueued.
+struct CollGroup {
+    int g0 = 0, n_images = 0;       // images [g0, g0 + n_images) of the collection
+    std::vector<mim_problem> pairs;  // [query set][image of the group]
+    KnnSchedule S, S8;               // Hamming / float pieces; the i8 units (128-D sets)
+    KnnCollLayout Lo;
+    size_t up_bytes() const {
+        return sizeof(TopkHamWork) * S.ham.size() + sizeof(TopkFltWork) * S.flt.size() + vec_bytes(S8.works) +
+               vec_bytes(S8.seg) + (sizeof(CollPart) + sizeof(CollI8Prob)) * pairs.size();
+    }
+};
+
+// With the lock held.  The problems of a group are its (query set, image) pairs; the work lists are those of
+// knn_hamming_plan / knn_float_plan (128-D sets at dim 128) and, for the 128-D sets again, the i8 units of
+// knn_schedule_static: a 128-D pair is in both lists, and the sets' integrality flags decide on the device
+// which kernel's blocks do its pairs (as radius_count_locked).
+static mim_status knn_collection_locked(mim_ctx* c, const int32_t* query_sets, int n_queries, const int32_t* train_sets,
+                                        int n_images, int k, int32_t* idx_dev, int32_t* img_dev, float* dist_dev) {
+    invalidate_batch(c);
+    c->rad.valid = false;
+    if (k < 1 || k > MIM_KNN_MAX_K)
+        return fail(c, MIM_EINVAL, "knn_collection: k must be 1..%d (got %d)", MIM_KNN_MAX_K, k);
+    if (n_images < 1 || n_images > kCollMaxImages)
+        return fail(c, MIM_EINVAL, "knn_collection: n_images must be 1..%d (got %d)", kCollMaxImages, n_images);
+    if (n_queries < 0 || (n_queries > 0 && !query_sets) || !train_sets)
+        return fail(c, MIM_EINVAL, "knn_collection: bad arguments");
+    if (n_queries == 0) return MIM_OK;
+    mim_status s = flush_preps(c);  // the 128-D sets' fragment tiles, norm blocks and flags
+    if (s != MIM_OK) return s;
+    s = device_limits(c);
+    if (s != MIM_OK) return s;
+    // every pair under the pairing rules, query set major
+    std::vector<mim_problem> pairs((size_t)n_queries * n_images);
+    for (int qi = 0; qi < n_queries; ++qi)
+        for (int j = 0; j < n_images; ++j) pairs[(size_t)qi * n_images + j] = mim_problem{query_sets[qi], train_sets[j]};
+    ProblemList L;
+    s = problem_list(c, pairs.data(), (int)pairs.size(), false, false, L);
+    if (s != MIM_OK) return s;
+    std::vector<int> nq(n_queries), nt(n_images);
+    long long rows = 0;
+    for (int qi = 0; qi < n_queries; ++qi) rows += nq[qi] = c->sets[query_sets[qi]].d.n;
+    for (int j = 0; j < n_images; ++j) nt[j] = c->sets[train_sets[j]].d.n;
+    if (rows > 0 && (!idx_dev || !img_dev || !dist_dev)) return fail(c, MIM_EINVAL, "knn_collection: null output");
+    if (rows == 0) return MIM_OK;
+    const SetRec& Q0 = c->sets[query_sets[0]];
+    const bool sift = Q0.is_sift();
+    const std::vector<int> start = knn_coll_groups(nq, nt, Q0.is_bin(), sift, k, coll_part_budget());
+    const int n_groups = (int)start.size() - 1;
+
+    std::vector<CollGroup> groups(n_groups);
+    size_t max_ham = 0, max_flt = 0, max_pairs = 0, max_w8 = 0, max_up = 0;
+    long long max_part = 1;
+    int i8_splits = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        CollGroup& G = groups[g];
+        G.g0 = start[g];
+        G.n_images = start[g + 1] - start[g];
+        const int gn = G.n_images, n = n_queries * gn;
+        G.pairs.resize((size_t)n);
+        std::vector<KnnSchedProblem> in((size_t)n);
+        for (int qi = 0; qi < n_queries; ++qi)
+            for (int j = 0; j < gn; ++j) {
+                G.pairs[(size_t)qi * gn + j] = pairs[(size_t)qi * n_images + G.g0 + j];
+                in[(size_t)qi * gn + j] = L.in[(size_t)qi * n_images + G.g0 + j];
+            }
+        G.S.slots.assign(n, KnnSchedSlot{});
+        knn_hamming_plan(in, c->n_cu, G.S);
+        knn_float_plan(in, c->n_cu, G.S);
+        if (sift) {
+            for (KnnSchedProblem& p : in) p.fdim = 0;  // the i8 schedule's view of the same pairs
+            G.S8.slots.assign(n, KnnSchedSlot{});
+            knn_schedule_static(in, c->knn_grid, -1, G.S8);
+            for (const KnnSchedSlot& sl : G.S8.slots) i8_splits = std::max(i8_splits, sl.nsplit);
+        }
+        G.Lo = knn_coll_offsets(nq, gn, G.S.slots, sift ? &G.S8.slots : nullptr, k);
+        max_ham = std::max(max_ham, G.S.ham.size());
+        max_flt = std::max(max_flt, G.S.flt.size());
+        max_pairs = std::max(max_pairs, G.pairs.size());
+        max_w8 = std::max(max_w8, vec_bytes(G.S8.works) + vec_bytes(G.S8.seg));
+        max_part = std::max(max_part, G.Lo.part);
+        max_up = std::max(max_up, G.up_bytes());
+    }
+    // every buffer at its largest before the first launch: none is reallocated under a group's kernels
+    HIPCHK(c, c->coll_parts.ensure(sizeof(TopkEnt) * max_part));
+    HIPCHK(c, c->coll_queries.ensure(sizeof(CollQuery) * n_queries));
+    HIPCHK(c, c->coll_tab.ensure(sizeof(CollPart) * max_pairs));
+    if (max_ham) HIPCHK(c, c->coll_ham_works.ensure(sizeof(TopkHamWork) * max_ham));
+    if (max_flt) HIPCHK(c, c->coll_flt_works.ensure(sizeof(TopkFltWork) * max_flt));
+    if (sift) HIPCHK(c, c->coll_i8_probs.ensure(sizeof(CollI8Prob) * max_pairs));
+    if (max_w8) HIPCHK(c, c->coll_i8_works.ensure(max_w8));
+    c->coll_groups = n_groups;
+    c->coll_i8_splits = i8_splits;
+    TopkEnt* const parts = c->coll_parts.as<TopkEnt>();
+    std::vector<CollQuery> queries(n_queries);
+    for (int qi = 0; qi < n_queries; ++qi) queries[qi] = CollQuery{groups[0].Lo.out_off[qi], nq[qi], 0};
+    c->cur = c->stream;
+    ev_mark(c, "begin");
+    for (int g = 0; g < n_groups; ++g) {
+        const CollGroup& G = groups[g];
+        const KnnCollLayout& Lo = G.Lo;
+        const int n = (int)G.pairs.size();
+        std::vector<TopkHamWork> ham;
+        ham.reserve(G.S.ham.size());
+        for (const HamPiece& hp : G.S.ham) {
+            const HamFields f = ham_fields(c, G.pairs[hp.problem]);
+            ham.push_back(TopkHamWork{f.q, f.t,
+                                      parts + Lo.part_off[hp.problem] + (long long)hp.split * G.S.slots[hp.problem].q_pad * k,
+                                      f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
+        }
+        std::vector<TopkFltWork> flt;
+        flt.reserve(G.S.flt.size());
+        for (const FltPiece& fp : G.S.flt) {
+            const SetRec &Q = c->sets[G.pairs[fp.problem].query_set], &T = c->sets[G.pairs[fp.problem].train_set];
+            const FltFields f = flt_fields(c, G.pairs[fp.problem]);
+            flt.push_back(TopkFltWork{f.q, f.t,
+                                      parts + Lo.part_off[fp.problem] + (long long)fp.split * G.S.slots[fp.problem].q_pad * k,
+                                      f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec, sift ? Q.d.flags : nullptr,
+                                      sift ? T.d.flags : nullptr});
+        }
+        std::vector<CollPart> tab(n);
+        std::vector<CollI8Prob> probs8(sift ? n : 0);
+        for (int i = 0; i < n; ++i) {
+            const SetRec &Q = c->sets[G.pairs[i].query_set], &T = c->sets[G.pairs[i].train_set];
+            tab[i] = CollPart{nullptr, parts + Lo.part_off[i], nullptr, nullptr, 0, 0, G.S.slots[i].nsplit,
+                              G.S.slots[i].q_pad, G.g0 + i % G.n_images, 0};
+            if (sift) {
+                tab[i].a = parts + Lo.part8_off[i];
+                tab[i].qflags = Q.d.flags;
+                tab[i].tflags = T.d.flags;
+                tab[i].na = 2 * G.S8.slots[i].nsplit;
+                tab[i].qa_pad = G.S8.slots[i].q_pad;
+                probs8[i] = CollI8Prob{Q.d, T.d, parts + Lo.part8_off[i], G.S8.slots[i].q_pad, 0};
+            }
+        }
+        // the device tables are rewritten in stream order (after the previous group's kernels)
+        StageWriter up(c->stage, max_up + vec_bytes(queries), c->stream);
+        if (g == 0) up.put(c->coll_queries, queries);
+        up.put(c->coll_tab, tab);
+        up.put(c->coll_ham_works, ham);
+        up.put(c->coll_flt_works, flt);
+        up.put(c->coll_i8_probs, probs8);
+        const size_t wb = vec_bytes(G.S8.works);
+        if (wb) up.put(c->coll_i8_works.p, G.S8.works.data(), wb, G.S8.seg.data(), vec_bytes(G.S8.seg));
+        HIPCHK(c, up.done());
+        ev_mark(c, "coll_upload");  // the table copies, outside the kernels' spans as in the other entries
+        launch_knn_topk_hamming(c->coll_ham_works.as<TopkHamWork>(), (int)ham.size(), k, c->cur);
+        launch_knn_topk_float(c->coll_flt_works.as<TopkFltWork>(), (int)flt.size(), k, c->cur);
+        if (wb) {
+            const KnnWork* w = c->coll_i8_works.as<KnnWork>();
+            launch_knn_topk_i8(c->coll_i8_probs.as<CollI8Prob>(), w, reinterpret_cast<const int*>(w + G.S8.works.size()),
+                               G.S8.n_blocks, k, c->cur);
+        }
+        HIPCHK(c, hipGetLastError());
+        ev_mark(c, "knn");
+        launch_knn_coll_merge(c->coll_queries.as<CollQuery>(), n_queries, c->coll_tab.as<CollPart>(), G.n_images, L.max_nq, k,
+                              g > 0, idx_dev, img_dev, dist_dev, c->cur);
+        HIPCHK(c, hipGetLastError());
+        ev_mark(c, "ratio");
+    }
+    return MIM_OK;
+}
+
+extern "C" {
+
+mim_status mim_knn_collection_dev(mim_ctx* c, const int32_t* query_sets, int32_t n_queries, const int32_t* train_sets,
+                                  int32_t n_images, int32_t k, int32_t* idx_dev, int32_t* img_dev, float* dist_dev) {
+    if (!c) return MIM_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return knn_collection_locked(c, query_sets, n_queries, train_sets, n_images, k, idx_dev, img_dev, dist_dev);
 }
 
 }  // extern "C"

@@ -377,6 +377,73 @@ inline KnnTopkLayout knn_topk_offsets(const std::vector<KnnSchedProblem>& in, co
     return Lo;
 }
 
+// Train collections (mim_knn_collection_dev).  The problems of a group of images are the
+// (query set, image) pairs, query set major: pair qi * n_images + j.  A pair's Hamming / float lists are
+// [nsplit][q_pad][k] entries as in knn_topk_offsets; a 128-D pair also has the i8 kernel's lists,
+// [2 nsplit8][q_pad8][kt] (slots8: the slots knn_schedule_static filled; two lists per split, one per lane
+// half; kt = k rounded up to 4, 8 or 16, the slots of the kernel's list), behind them.  Query set qi's output rows start at k times the query rows before it, whatever the group.
+struct KnnCollLayout {
+    std::vector<long long> part_off;   // per pair: its Hamming / float lists
+    std::vector<long long> part8_off;  // per pair: its i8 lists (with slots8)
+    std::vector<long long> out_off;    // per query set
+    long long part = 0, out = 0;       // totals, in entries
+};
+inline KnnCollLayout knn_coll_offsets(const std::vector<int>& nq, int n_images, const std::vector<KnnSchedSlot>& slots,
+                                      const std::vector<KnnSchedSlot>* slots8, int k) {
+    KnnCollLayout Lo;
+    const int kt = k <= 4 ? 4 : k <= 8 ? 8 : 16;
+    const size_t n = nq.size() * (size_t)n_images;
+    Lo.part_off.resize(n);
+    Lo.part8_off.assign(n, -1);
+    Lo.out_off.resize(nq.size());
+    for (size_t qi = 0; qi < nq.size(); ++qi) {
+        Lo.out_off[qi] = Lo.out;
+        Lo.out += (long long)std::max(nq[qi], 0) * k;
+        for (int j = 0; j < n_images; ++j) {
+            const size_t i = qi * n_images + j;
+            Lo.part_off[i] = Lo.part;
+            Lo.part += (long long)slots[i].nsplit * slots[i].q_pad * k;
+            if (slots8) {
+                Lo.part8_off[i] = Lo.part;
+                Lo.part += 2LL * (*slots8)[i].nsplit * (*slots8)[i].q_pad * kt;
+            }
+        }
+    }
+    return Lo;
+}
+
+// The most entries the lists of one (query set, image) pair can take under any plan: knn_hamming_plan and
+// knn_float_plan cut at most units / 4 splits (units of kHamTileRows or kFltRowPad rows), and
+// knn_schedule_static cuts a query block's n_tiles at multiples of a sub-chunk of at least kKnnMinChunk tiles:
+// at most n_tiles / kKnnMinChunk + 2 pieces.
+inline long long knn_coll_pair_bound(int nq, int nt, bool bin, bool sift, int k) {
+    const int unit = bin ? kHamTileRows : kFltRowPad, blockq = bin ? kHamBlockQ : kFltBlockQ;
+    const long long splits = std::max(1, (nt + unit - 1) / unit / 4);
+    long long e = splits * std::max((nq + blockq - 1) / blockq, 1) * blockq * k;
+    if (sift) e += 2LL * ((nt + 63) / 64 / kKnnMinChunk + 2) * knn_query_blocks(nq) * kKnnBlockQ * (k <= 4 ? 4 : k <= 8 ? 8 : 16);
+    return e;
+}
+
+// Images in groups whose partial lists fit `budget` bytes by that bound (8 bytes per entry), so that the
+// partial buffer does not grow with the collection: group g is images [start[g], start[g + 1]).  An image
+// that alone exceeds the budget is a group of its own.
+inline std::vector<int> knn_coll_groups(const std::vector<int>& nq, const std::vector<int>& nt, bool bin, bool sift, int k,
+                                        long long budget) {
+    std::vector<int> start{0};
+    long long used = 0;
+    for (size_t j = 0; j < nt.size(); ++j) {
+        long long e = 0;
+        for (int q : nq) e += knn_coll_pair_bound(q, nt[j], bin, sift, k);
+        if (used > 0 && (used + e) * 8 > budget) {
+            start.push_back((int)j);
+            used = 0;
+        }
+        used += e;
+    }
+    start.push_back((int)nt.size());
+    return start;
+}
+
 // G: resident distance-kernel blocks of the device.
 inline KnnSchedule knn_schedule(const std::vector<KnnSchedProblem>& in, int G, int n_cu, int max_iters,
                                 const KnnSchedKnobs& knobs) {

@@ -327,6 +327,9 @@ template <int KT>
 __global__ __launch_bounds__(kFltThreads) void knn_topk_float_kernel(const TopkFltWork* __restrict__ works, int k) {
     __shared__ __attribute__((aligned(16))) float lds[kFltLdsFloats];
     const TopkFltWork w = works[blockIdx.x];
+    // collection calls on 128-D sets that are integer-valued on both sides: the i8 kernel's (block-uniform, as
+    // radius_float_kernel); null from the other entries
+    if (w.qflags && !(*w.qflags | *w.tflags)) return;
     if ((w.dim & 15) == 0 && w.dim <= 128 && w.dp == w.dim) {  // block-uniform
         switch (w.dim >> 4) {
             case 1: flt_topk_resident<1, KT>(w, k, lds); break;

@@ -135,6 +135,10 @@ struct TopkFltWork {
     int dp;              // floats per stored row
     int nt;              // train rows: no row from nt on is read
     int vec;             // both row pointers are 16-byte aligned (dp is a multiple of 4): float4 loads
+    // mim_knn_collection_dev: the 128-D sets' integrality flags (SetDev::flags); a block returns
+    // at once when both say integer-valued, the i8 top-k kernel owns those pairs.  Null from every other entry.
+    const int* qflags;
+    const int* tflags;
 };
 
 // One problem of the top-k merge and emit kernel.

@@ -147,7 +147,7 @@ class Matcher:
             if desc.shape[0] <= 1 or desc.strides[1] != 1 or desc.strides[0] < desc.shape[1]:
                 desc = np.ascontiguousarray(desc)  # anything but rows of unit-stride bytes a fixed step apart
             kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 2)
-            step = int(desc.strides[0])
+            step = int(desc.strides[0]) if desc.shape[0] > 1 else int(desc.shape[1])  # an empty array's stride may be 0
         else:
             import torch
             desc = desc_u8
@@ -689,6 +689,39 @@ class Matcher:
         arr = np.ascontiguousarray(arr, np.int32).reshape(-1, 2)
         self._check(self.L.mim_knn_batch_dev(self._ctx, arr.ctypes.data_as(C.POINTER(Problem)), len(arr), k,
                                              C.c_void_p(_lib.ptr(idx_dev)), C.c_void_p(_lib.ptr(dist_dev))))
+
+    # ---- knnMatch over a train collection ---------------------------------------
+    def knn_collection_dev(self, query_sets, train_sets, k: int, idx_dev, img_dev, dist_dev):
+        """mim_knn_collection_dev: every query set against the collection train_sets (image j = train_sets[j]), the k
+        nearest rows over all images per query row, asynchronous; query set i's rows start at entry
+        k * (rows of the query sets before it) of the three device buffers (trainIdx, imgIdx, distance)."""
+        k = self._check_k(k)
+        qs = np.ascontiguousarray(np.asarray(list(query_sets), np.int32).reshape(-1))
+        ts = np.ascontiguousarray(np.asarray(list(train_sets), np.int32).reshape(-1))
+        self._check(self.L.mim_knn_collection_dev(self._ctx, C.c_void_p(qs.ctypes.data), len(qs), C.c_void_p(ts.ctypes.data),
+                                                  len(ts), k, C.c_void_p(_lib.ptr(idx_dev)), C.c_void_p(_lib.ptr(img_dev)),
+                                                  C.c_void_p(_lib.ptr(dist_dev))))
+
+    def knn_match_collection(self, query_set: int, train_sets, k: int = 2, nq: int | None = None):
+        """BFMatcher::add(views) + knnMatch(query, matches, k) on registered sets -> per query row a list of DMatch
+        with imgIdx filled (absent entries dropped).  nq: the query set's rows, needed only for a set this object
+        did not register itself."""
+        import torch
+        k = self._check_k(k)
+        if nq is None:
+            nq = self._set_rows.get(int(query_set))
+        if nq is None:
+            raise ValueError(f"knn_match_collection: the row count of set {query_set} is not known here: pass nq")
+        dev = torch.device("cuda", self.device)
+        idx = torch.full((max(nq, 1), k), -1, dtype=torch.int32, device=dev)
+        img = torch.full((max(nq, 1), k), -1, dtype=torch.int32, device=dev)
+        dist = torch.zeros((max(nq, 1), k), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the fills, before the matcher's stream writes
+        self.knn_collection_dev([int(query_set)], train_sets, k, idx, img, dist)
+        self.synchronize()
+        idx, img, dist = idx.cpu().numpy()[:nq], img.cpu().numpy()[:nq], dist.cpu().numpy()[:nq]
+        return [[DMatch(i, int(idx[i, j]), int(img[i, j]), float(dist[i, j])) for j in range(k) if idx[i, j] >= 0]
+                for i in range(nq)]
 
     # ---- radiusMatch (DESIGN.md §17) ----------------------------------------------------------
     @staticmethod

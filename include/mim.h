@@ -293,6 +293,26 @@ mim_status mim_knn_l2(struct mim_ctx* ctx, const float* q, int32_t nq, const flo
 mim_status mim_knn_hamming(struct mim_ctx* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt,
                            int32_t width, int32_t k, int32_t* idx, float* dist);
 
+/* ---- knnMatch over a train collection (BFMatcher::add(views); knnMatch(query, matches, k)) --------
+ * Every query set is matched against the same collection of n_images registered sets, image j being
+ * train_sets[j].  For every query row the k smallest over all images under (DMatch::distance as float32,
+ * imgIdx, trainIdx), ascending: what OpenCV's per-image insertion with update = imgIdx << 18 leaves (an equal
+ * distance never passes an earlier image or row).  Distances carry the bits of the other entries of the kind,
+ * float rows (integer 128-D rows included) are ranked on the sqrtf value, a distance not below FLT_MAX is
+ * never inserted, and an absent entry is trainIdx -1, imgIdx -1, distance FLT_MAX.  Asynchronous on the ctx
+ * stream.  idx_dev / img_dev / dist_dev: device buffers of k * (nq_0 + ... + nq_{n_queries-1}) entries; query
+ * set i's rows start at entry k * (nq_0 + ... + nq_{i-1}).  Sets of any one kind; a query set and every image
+ * pair under the rules and errors of mim_batch_run (problem i * n_images + j in the messages).  MIM_EINVAL
+ * with a text: k outside 1..MIM_KNN_MAX_K, n_images outside 1..8191 (OpenCV: imgCount << 18 below INT_MAX), a
+ * null output while there are query rows, a train set of 2^18 rows or more.  An image without rows
+ * contributes nothing.  The images are processed in groups whose partial lists fit a byte budget (256 MiB;
+ * MIM_COLL_PART_BYTES, read per call, overrides it), so the workspace does not grow with the collection.
+ * Integer-valued 128-D sets run on the i8 MFMA top-k kernel.  Like the other primitives the call leaves the
+ * ctx without a batch and without a radius count to fill.  Masks are not supported. */
+mim_status mim_knn_collection_dev(struct mim_ctx* ctx, const int32_t* query_sets, int32_t n_queries,
+                                  const int32_t* train_sets, int32_t n_images, int32_t k, int32_t* idx_dev,
+                                  int32_t* img_dev, float* dist_dev);
+
 /* ---- radiusMatch (BFMatcher(norm).radiusMatch(q, t, matches, maxDistance)) -----------------------
  * For every query row every train row with DMatch::distance <= max_distance, the test being the float32
  * compare of the distance against the float max_distance (a NaN distance never matches, an overflowed +inf
