@@ -797,25 +797,34 @@ static mim_status problem_list(mim_ctx* c, const mim_problem* problems, int n, b
     return MIM_OK;
 }
 
-// What every work item of a problem's Hamming pieces shares, and what every one of its float pieces does; the
-// callers add the piece's rows and where its results go.
-struct HamFields {
-    const uint32_t *q, *t;  // the padded rows
-    int nq, wdw;            // query rows, dwords per padded row
-};
-static HamFields ham_fields(const mim_ctx* c, const mim_problem& pr) {
+// The sweep's part of a work item (HamSweepWork, FltSweepWork): a piece of knn_hamming_plan / knn_float_plan with
+// its problem's rows.  flags: a 128-D problem's pieces carry the sets' integrality flags (an i8 kernel runs too).
+static HamSweepWork ham_sweep_work(const mim_ctx* c, const mim_problem& pr, const HamPiece& hp) {
     const SetRec &Q = c->sets[pr.query_set], &T = c->sets[pr.train_set];
-    return HamFields{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag), Q.d.n,
-                     Q.bin_pad / 4};
+    return HamSweepWork{reinterpret_cast<const uint32_t*>(Q.d.frag), reinterpret_cast<const uint32_t*>(T.d.frag), Q.d.n,
+                        hp.q0, hp.r0, hp.r1, Q.bin_pad / 4};
 }
-struct FltFields {
-    const float *q, *t;
-    int nq, dim, dp, nt, vec;  // vec: both row pointers are 16-byte aligned (the stride is a multiple of 4 floats)
-};
-static FltFields flt_fields(const mim_ctx* c, const mim_problem& pr) {
+static FltSweepWork flt_sweep_work(const mim_ctx* c, const mim_problem& pr, const FltPiece& fp, bool flags) {
     const SetRec &Q = c->sets[pr.query_set], &T = c->sets[pr.train_set];
-    return FltFields{Q.d.f32, T.d.f32, Q.d.n, Q.flt_dim(), Q.flt_stride(), T.d.n,
-                     (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0 ? 1 : 0};
+    const bool fl = flags && Q.is_sift();
+    return FltSweepWork{Q.d.f32, T.d.f32, fl ? Q.d.flags : nullptr, fl ? T.d.flags : nullptr, Q.d.n, fp.q0, fp.r0, fp.r1,
+                        Q.flt_dim(), Q.flt_stride(), T.d.n, (((uintptr_t)Q.d.f32 | (uintptr_t)T.d.f32) & 15) == 0 ? 1 : 0};
+}
+// A schedule's pieces as the work items of a top-k or radius kernel: the sweep's part and dest(problem, split)
+template <class Work, class Dest>
+static std::vector<Work> ham_works(const mim_ctx* c, const mim_problem* problems, const KnnSchedule& S, Dest dest) {
+    std::vector<Work> v;
+    v.reserve(S.ham.size());
+    for (const HamPiece& hp : S.ham) v.push_back(Work{ham_sweep_work(c, problems[hp.problem], hp), dest(hp.problem, hp.split)});
+    return v;
+}
+template <class Work, class Dest>
+static std::vector<Work> flt_works(const mim_ctx* c, const mim_problem* problems, const KnnSchedule& S, bool flags, Dest dest) {
+    std::vector<Work> v;
+    v.reserve(S.flt.size());
+    for (const FltPiece& fp : S.flt)
+        v.push_back(Work{flt_sweep_work(c, problems[fp.problem], fp, flags), dest(fp.problem, fp.split)});
+    return v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -898,9 +907,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     ham.reserve(S.ham.size());
     for (const HamPiece& hp : S.ham) {
         const ProbDev& P = c->h_probs[hp.problem];
-        const HamFields f = ham_fields(c, problems[hp.problem]);
-        const HamWork hw{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, f.nq, hp.q0, hp.r0,
-                         hp.r1, f.wdw, 0};
+        const HamSweepWork f = ham_sweep_work(c, problems[hp.problem], hp);
+        const HamWork hw{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)hp.split * P.q_pad, f.nq, f.q0, f.r0,
+                         f.r1, f.wdw, 0};
         if (filter != 0 && hp.problem < n_user && shadow_of[hp.problem] < 0)
             hamx.push_back(HamCrossWork{hw, c->colmin.as<uint32_t>() + col_off[hp.problem]});
         else
@@ -913,9 +922,9 @@ static mim_status build_tables(mim_ctx* c, const mim_problem* user_problems, int
     flt.reserve(S.flt.size());
     for (const FltPiece& fp : S.flt) {
         const ProbDev& P = c->h_probs[fp.problem];
-        const FltFields f = flt_fields(c, problems[fp.problem]);
-        flt.push_back(FltWork{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)fp.split * P.q_pad, f.nq, fp.q0,
-                              fp.r0, fp.r1, f.dim, f.dp});
+        const FltSweepWork f = flt_sweep_work(c, problems[fp.problem], fp, false);
+        flt.push_back(FltWork{f.q, f.t, c->parts.as<Top2>() + P.part_off + (long long)fp.split * P.q_pad, f.nq, f.q0,
+                              f.r0, f.r1, f.dim, f.dp});
     }
     if (!flt.empty()) HIPCHK(c, c->flt_works.ensure(sizeof(FltWork) * flt.size()));
     HIPCHK(c, c->good_q.ensure(sizeof(int32_t) * good));
@@ -1228,22 +1237,9 @@ static mim_status knn_topk_locked(mim_ctx* c, const mim_problem* problems, int n
     for (int i = 0; i < n; ++i)
         probs[i] = TopkProb{parts + Lo.part_off[i], idx_dev + Lo.out_off[i], dist_dev + Lo.out_off[i], in[i].nq,
                             S.slots[i].nsplit, S.slots[i].q_pad, 0};
-    std::vector<TopkHamWork> ham;
-    ham.reserve(S.ham.size());
-    for (const HamPiece& hp : S.ham) {
-        const HamFields f = ham_fields(c, problems[hp.problem]);
-        ham.push_back(TopkHamWork{f.q, f.t,
-                                  parts + Lo.part_off[hp.problem] + (long long)hp.split * S.slots[hp.problem].q_pad * k,
-                                  f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
-    }
-    std::vector<TopkFltWork> flt;
-    flt.reserve(S.flt.size());
-    for (const FltPiece& fp : S.flt) {
-        const FltFields f = flt_fields(c, problems[fp.problem]);
-        flt.push_back(TopkFltWork{f.q, f.t,
-                                  parts + Lo.part_off[fp.problem] + (long long)fp.split * S.slots[fp.problem].q_pad * k,
-                                  f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec, nullptr, nullptr});
-    }
+    const auto out = [&](int p, int split) { return parts + Lo.part_off[p] + (long long)split * S.slots[p].q_pad * k; };
+    const std::vector<TopkHamWork> ham = ham_works<TopkHamWork>(c, problems, S, out);
+    const std::vector<TopkFltWork> flt = flt_works<TopkFltWork>(c, problems, S, false, out);
     if (!ham.empty()) HIPCHK(c, c->topk_ham_works.ensure(sizeof(TopkHamWork) * ham.size()));
     if (!flt.empty()) HIPCHK(c, c->topk_flt_works.ensure(sizeof(TopkFltWork) * flt.size()));
     // the device tables are rewritten in stream order (after the previous call's kernels)
@@ -1440,24 +1436,9 @@ static mim_status knn_collection_locked(mim_ctx* c, const int32_t* query_sets, i
         const CollGroup& G = groups[g];
         const KnnCollLayout& Lo = G.Lo;
         const int n = (int)G.pairs.size();
-        std::vector<TopkHamWork> ham;
-        ham.reserve(G.S.ham.size());
-        for (const HamPiece& hp : G.S.ham) {
-            const HamFields f = ham_fields(c, G.pairs[hp.problem]);
-            ham.push_back(TopkHamWork{f.q, f.t,
-                                      parts + Lo.part_off[hp.problem] + (long long)hp.split * G.S.slots[hp.problem].q_pad * k,
-                                      f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
-        }
-        std::vector<TopkFltWork> flt;
-        flt.reserve(G.S.flt.size());
-        for (const FltPiece& fp : G.S.flt) {
-            const SetRec &Q = c->sets[G.pairs[fp.problem].query_set], &T = c->sets[G.pairs[fp.problem].train_set];
-            const FltFields f = flt_fields(c, G.pairs[fp.problem]);
-            flt.push_back(TopkFltWork{f.q, f.t,
-                                      parts + Lo.part_off[fp.problem] + (long long)fp.split * G.S.slots[fp.problem].q_pad * k,
-                                      f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec, sift ? Q.d.flags : nullptr,
-                                      sift ? T.d.flags : nullptr});
-        }
+        const auto out = [&](int p, int split) { return parts + Lo.part_off[p] + (long long)split * G.S.slots[p].q_pad * k; };
+        const std::vector<TopkHamWork> ham = ham_works<TopkHamWork>(c, G.pairs.data(), G.S, out);
+        const std::vector<TopkFltWork> flt = flt_works<TopkFltWork>(c, G.pairs.data(), G.S, true, out);
         std::vector<CollPart> tab(n);
         std::vector<CollI8Prob> probs8(sift ? n : 0);
         for (int i = 0; i < n; ++i) {
@@ -1570,20 +1551,9 @@ static mim_status radius_count_locked(mim_ctx* c, const mim_problem* problems, i
     knn_hamming_plan(in, c->n_cu, S);
     knn_float_plan(in, c->n_cu, S);
     knn_schedule_static(in8, c->knn_grid, -1, S8);
-    std::vector<RadHamWork> ham;
-    ham.reserve(S.ham.size());
-    for (const HamPiece& hp : S.ham) {
-        const HamFields f = ham_fields(c, problems[hp.problem]);
-        ham.push_back(RadHamWork{f.q, f.t, qoff[hp.problem], f.nq, hp.q0, hp.r0, hp.r1, f.wdw, 0});
-    }
-    std::vector<RadFltWork> flt;
-    flt.reserve(S.flt.size());
-    for (const FltPiece& fp : S.flt) {
-        const SetRec &Q = c->sets[problems[fp.problem].query_set], &T = c->sets[problems[fp.problem].train_set];
-        const FltFields f = flt_fields(c, problems[fp.problem]);
-        flt.push_back(RadFltWork{f.q, f.t, Q.is_sift() ? Q.d.flags : nullptr, Q.is_sift() ? T.d.flags : nullptr,
-                                 qoff[fp.problem], f.nq, fp.q0, fp.r0, fp.r1, f.dim, f.dp, f.nt, f.vec});
-    }
+    const auto first = [&](int p, int) { return qoff[p]; };
+    const std::vector<RadHamWork> ham = ham_works<RadHamWork>(c, problems, S, first);
+    const std::vector<RadFltWork> flt = flt_works<RadFltWork>(c, problems, S, true, first);
     std::vector<RadI8Prob> probs(n);
     for (int i = 0; i < n; ++i)
         probs[i] = RadI8Prob{c->sets[problems[i].query_set].d, c->sets[problems[i].train_set].d, qoff[i]};

@@ -12,25 +12,16 @@
 #include <climits>
 
 #include "mim_internal.h"
+#include "sweep_hamming.h"  // kHamThreads, kHamWaves, popc_add
 
 namespace mim {
 
 namespace {
 
-constexpr int kHamThreads = 256;                  // 4 waves
-constexpr int kHamWaves = kHamThreads / kWave;
 constexpr int kHamQPT = kHamBlockQ / kWave;       // query rows held by one lane
 constexpr uint32_t kHamNone = 0xFFFFFFFFu;        // packed-key sentinel: no row
 static_assert(kHamQPT * kWave == kHamBlockQ, "a block's queries are whole waves of lanes");
 static_assert(kHamTileRows * 64 >= kHamWaves * kHamBlockQ * 8, "the merge scratch reuses the tile's LDS");
-
-// popcount(x) + acc as the one instruction it is (left to the compiler, the sums are reassociated into
-// popcounts plus separate three-operand adds: 23 instead of 20 VALU instructions per pair at 32 bytes)
-__device__ __forceinline__ uint32_t popc_add(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 
 // Minimum of x over the wave's 64 lanes, in registers: four row_shr steps leave each 16-lane row's
 // minimum in its lane 15, row_bcast:15 carries it into rows 1 and 3, row_bcast:31 into rows 2 and 3;

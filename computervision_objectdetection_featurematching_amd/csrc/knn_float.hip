@@ -25,18 +25,12 @@
 #include <cfloat>
 #include <climits>
 
-#include "knn_float_arith.h"  // flt_round, flt_reduce, flt_tail4, flt_tile_rows; fp contraction off
 #include "mim_internal.h"
+#include "sweep_float.h"  // kFltThreads, kFltLdsFloats, kFltR; the arithmetic of knn_float_arith.h, fp contraction off
 
 namespace mim {
 
 namespace {
-
-constexpr int kFltThreads = 256;       // 4 waves, a query per lane
-constexpr int kFltLdsFloats = 8192;    // 32 KiB train tile
-constexpr int kFltR = 4;               // train rows in flight on the streamed path
-static_assert(kFltThreads == kFltBlockQ, "one query per thread");
-static_assert(kFltRowPad * 128 <= kFltLdsFloats && 16 * kFltMaxDim <= kFltLdsFloats, "tile fits the LDS");
 
 struct FltTop {
     float k1, k2;      // the two smallest distances (sqrt values)

@@ -6,6 +6,7 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define MIM_TOPK_HD __host__ __device__ __forceinline__
@@ -80,5 +81,13 @@ MIM_TOPK_UNROLL
 
 // the list length a k runs at: k rounded up to 4, 8 or 16
 inline int topk_kt(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : 16; }
+
+// f(std::integral_constant<int, topk_kt(k)>{}): the launchers' choice of a kernel's KT
+template <class F>
+inline void topk_dispatch(int k, F&& f) {
+    if (k <= 4) f(std::integral_constant<int, 4>{});
+    else if (k <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
 
 }  // namespace mim

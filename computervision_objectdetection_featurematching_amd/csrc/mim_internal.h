@@ -106,28 +106,28 @@ struct FltWork {
     int dp;              // floats per stored row: dim rounded up to a multiple of 4
 };
 
-// Top-k entries (knn_topk.hip): mim_knn_batch_dev and what is built on it.  The work items are
-// the pieces of knn_hamming_plan / knn_float_plan; a piece writes its queries' sorted lists of k entries to
-// the split's share of the top-k partials, [q_pad][k] TopkEnt.
+// The shared sweeps (sweep_hamming.h, sweep_float.h): one piece of knn_hamming_plan /
+// knn_float_plan, without where its results go.  The top-k and radius work items are this plus that.
 
-// Work item of the Hamming top-k kernel: as HamWork.
-struct TopkHamWork {
+// kHamBlockQ queries from q0 x train rows [r0, r1) of one problem; r0 is a multiple of kHamTileRows.
+struct HamSweepWork {
     const uint32_t* q;   // padded query rows of the problem
     const uint32_t* t;   // padded train rows
-    TopkEnt* out;        // the split's lists: the problem's partials + split * q_pad * k
     int nq;
     int q0;
     int r0, r1;
     int wdw;             // dwords per padded row: 4, 8 or 16
-    int pad_;
 };
 
-// Work item of the float top-k kernel: as FltWork, for generic float sets and for the f32 rows of 128-D
-// sets (dim = dp = 128), whose storage ends at row nt and whose pointers the caller may have borrowed us.
-struct TopkFltWork {
+// kFltBlockQ queries from q0 x train rows [r0, r1) of one problem, for generic float sets and for the f32 rows
+// of 128-D sets (dim = dp = 128), whose storage ends at row nt and whose pointers the caller may have borrowed us.
+struct FltSweepWork {
     const float* q;
     const float* t;
-    TopkEnt* out;
+    // the 128-D sets' integrality flags (SetDev::flags) where an i8 MFMA kernel runs beside the float one: a
+    // block returns at once when both say integer-valued, the i8 kernel owns those pairs.  Null otherwise.
+    const int* qflags;
+    const int* tflags;
     int nq;
     int q0;
     int r0, r1;
@@ -135,10 +135,17 @@ struct TopkFltWork {
     int dp;              // floats per stored row
     int nt;              // train rows: no row from nt on is read
     int vec;             // both row pointers are 16-byte aligned (dp is a multiple of 4): float4 loads
-    // mim_knn_collection_dev: the 128-D sets' integrality flags (SetDev::flags); a block returns
-    // at once when both say integer-valued, the i8 top-k kernel owns those pairs.  Null from every other entry.
-    const int* qflags;
-    const int* tflags;
+};
+
+// Top-k entries (knn_topk.hip): mim_knn_batch_dev and what is built on it.  A piece writes its
+// queries' sorted lists of k entries to the split's share of the top-k partials, [q_pad][k] TopkEnt.
+struct TopkHamWork {
+    HamSweepWork s;
+    TopkEnt* out;        // the split's lists: the problem's partials + split * q_pad * k
+};
+struct TopkFltWork {
+    FltSweepWork s;
+    TopkEnt* out;
 };
 
 // One problem of the top-k merge and emit kernel.

@@ -19,33 +19,15 @@ struct RadArgs {
     int pad_;
 };
 
-// Work item of the Hamming kernel: the piece of knn_hamming_plan (as HamWork).
+// Work items of the Hamming and float kernels: the piece of knn_hamming_plan / knn_float_plan and the problem's
+// first query.  A 128-D problem's float pieces carry the sets' flags.
 struct RadHamWork {
-    const uint32_t* q;  // padded query rows of the problem
-    const uint32_t* t;  // padded train rows
+    HamSweepWork s;
     long long qoff;
-    int nq;
-    int q0;
-    int r0, r1;
-    int wdw;            // dwords per padded row: 4, 8 or 16
-    int pad_;
 };
-
-// Work item of the float kernel: the piece of knn_float_plan (as TopkFltWork), for generic float sets and for
-// the f32 rows of 128-D sets, whose blocks return at once when both sets' flags say integer-valued.
 struct RadFltWork {
-    const float* q;
-    const float* t;
-    const int* qflags;  // the 128-D sets' integrality flags (SetDev::flags); null for generic float sets
-    const int* tflags;
+    FltSweepWork s;
     long long qoff;
-    int nq;
-    int q0;
-    int r0, r1;
-    int dim;            // floats per row as the caller gave them (1..kFltMaxDim)
-    int dp;             // floats per stored row
-    int nt;             // train rows: no row from nt on is read
-    int vec;            // both row pointers are 16-byte aligned (dp is a multiple of 4): float4 loads
 };
 
 // One problem of the i8 MFMA kernel, whose work items are the KnnWork units of knn_schedule_static.

@@ -122,6 +122,12 @@ def test_shapes(matcher, kind, nq, nt):
     assert sizes[2] == 0 and sizes[4] == nq * nt and sizes[1] < sizes[0]
 
 
+# a second i8 query block of one problem (512 queries to a block): its second wave has one valid column tile
+# with one valid column, and the three train tiles take two stages
+def test_second_query_block(matcher):
+    test_shapes(matcher, "sift_int", 577, 129)
+
+
 def test_host_entry_at_dim_128_takes_either_path(matcher):
     """mim_radius_l2 at dim 128 registers its private sets through the 128-D path: integer rows (the MFMA kernel)
     and non-integer rows (the float kernel) both give the yardstick's bits."""
