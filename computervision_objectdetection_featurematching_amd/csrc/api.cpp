@@ -206,7 +206,7 @@ namespace mim {
 // RANSAC workspace (definition shared with ransac.hip through this layout)
 struct RansacWs {
     DevBuf state, samples, hyp, counts, bounds, flags, irr_bits, irr, irr_cnt, cls, cls_tab, pass_bits, defer, defer_n, chains, best_h, cand, ncand, cex, cH, decided, stream,
-        scratch, inl, tiles, tbox, perm, surv, nsurv, err;
+        scratch, inl, tiles, tbox, perm, surv, nsurv, strip, err;
     long long stream_len = 0;
 };
 }  // namespace mim
@@ -400,7 +400,7 @@ void mim_ctx_destroy(mim_ctx* c) {
     c->arena.release();
     for (DevBuf* b : {&c->probs, &c->works, &c->parts, &c->good_q, &c->good_t, &c->pts, &c->n_good,
                       &c->results, &c->masks, &c->knn_idx, &c->knn_dist, &c->inl_tab, &c->inl_out, &c->knn_ctr, &c->ham_works, &c->flt_works, &c->ham_cross_works, &c->colmin, &c->cross_tab, &c->topk_parts, &c->topk_ham_works, &c->topk_flt_works, &c->topk_probs, &c->coll_parts, &c->coll_ham_works, &c->coll_flt_works, &c->coll_i8_probs, &c->coll_i8_works, &c->coll_tab, &c->coll_queries, &c->rad_counts, &c->rad_cursor, &c->rad_offsets, &c->rad_meta, &c->rad_keys, &c->rad_scratch, &c->rad_ham_works, &c->rad_flt_works, &c->rad_i8_works, &c->rad_probs, &c->rws.state, &c->rws.samples,
-                      &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.tbox, &c->rws.perm, &c->rws.surv, &c->rws.nsurv, &c->rws.err, &c->prep_jobs})
+                      &c->rws.hyp, &c->rws.counts, &c->rws.bounds, &c->rws.flags, &c->rws.irr_bits, &c->rws.irr, &c->rws.irr_cnt, &c->rws.cls, &c->rws.cls_tab, &c->rws.pass_bits, &c->rws.defer, &c->rws.defer_n, &c->rws.chains, &c->rws.best_h, &c->rws.cand, &c->rws.ncand, &c->rws.cex, &c->rws.cH, &c->rws.decided, &c->rws.stream, &c->rws.scratch, &c->rws.inl, &c->rws.tiles, &c->rws.tbox, &c->rws.perm, &c->rws.surv, &c->rws.nsurv, &c->rws.strip, &c->rws.err, &c->prep_jobs})
         b->release();
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
@@ -2073,6 +2073,7 @@ static mim_status ransac_prepare(mim_ctx* c, int n, const mim_params* prm, Ransa
     // the survivor list of the capped bound holds a whole chunk per problem
     HIPCHK(c, c->rws.surv.ensure(sizeof(int) * it_total));
     HIPCHK(c, c->rws.nsurv.ensure(sizeof(int) * std::max(n, 1)));
+    HIPCHK(c, c->rws.strip.ensure(sizeof(int4) * std::max(n, 1)));
     HIPCHK(c, c->rws.err.ensure(sizeof(int) * 4));
     HIPCHK(c, c->results.ensure(sizeof(mim_result) * std::max(n, 1)));
     HIPCHK(c, c->masks.ensure(good_total));
@@ -2113,6 +2114,7 @@ static mim_status ransac_prepare(mim_ctx* c, int n, const mim_params* prm, Ransa
     b.perm = c->rws.perm.as<int>();
     b.surv = c->rws.surv.as<int>();
     b.nsurv = c->rws.nsurv.as<int>();
+    b.strip = c->rws.strip.as<int4>();
     b.err = c->rws.err.as<int>();
     if (c->samp_on < 0) {
         const char* e = getenv("MIM_SAMPLER_STREAM");
@@ -2164,6 +2166,7 @@ static mim_status ransac_enqueue_range(mim_ctx* c, int p0, int np, const RansacB
     g.cH += 9LL * p0 * 2 * kCandPerProblem;
     g.decided += (long long)p0 * 2 * kCandPerProblem;
     g.nsurv += p0;
+    g.strip += p0;
     ransac_enqueue(rp, np, c->probs.as<ProbDev>() + p0, c->pts.as<float4>(), c->n_good.as<int>() + p0, g,
                    c->masks.as<uint8_t>(), c->results.as<mim_result>() + p0, raw, c->cur, mark_cb, c, c->exact_all);
     HIPCHK(c, hipGetLastError());

@@ -260,6 +260,8 @@ struct RansacBufs {
     int* perm;                // [2 * good_off ..][2][n] scratch of the tiles' order (arrival order, row -> point)
     int* surv;                // [it_off + k] iterations of the chunk whose capped upper bound beats the bar
     int* nsurv;               // [problem] how many are listed
+    int4* strip;              // [problem] strip pre-stage: (bar B, strip records stand, iterations above the bar,
+                              // largest pilot count), ransac_strip_pilot_kernel
     int* err;                 // device error word (bit0: RNG stream exhausted)
     // Sampler stream: the getSubset replay of chunk c+1 runs on s2 concurrently with the bound /
     // candidate / exact / replay kernels of chunk c (null: everything on the caller's stream)

@@ -743,7 +743,7 @@ __device__ __forceinline__ bool check_subset_fp32(const float* s, const float* d
 // ------------------------------------------------------------------------------------------------
 // RANSACUpdateNumIters (ptsetreg.cpp)
 // ------------------------------------------------------------------------------------------------
-__device__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
+__host__ __device__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
     p = p > 0. ? p : 0.;
     p = p < 1. ? p : 1.;
     ep = ep > 0. ? ep : 0.;
@@ -756,6 +756,21 @@ __device__ int update_num_iters(double p, double ep, int model_points, int max_i
     denom = log(denom);
     if (denom >= 0 || -num >= max_iters * (-denom)) return max_iters;
     return (int)rint(num / denom);  // cvRound
+}
+
+// The largest inlier count of an n-point problem that leaves the loop at max_iters: the largest c with
+// update_num_iters(conf, (n - c) / n, 4, max_iters) == max_iters, ep formed as the replay forms it.  The
+// returned bound falls with the count (the capped branch compares -log(1 - conf) with max_iters times
+// -log(1 - (c / n)^4), which grows by a relative 4 / c per count, far above the functions' rounding), so
+// a bisection finds it; c = 0 always qualifies (denom = 1, log = 0).  Host and device: the device's value
+// is the one the strip pre-stage uses beside the replay's own calls, the host's is a test hook.
+__host__ __device__ inline int free_level(int n, double conf, int max_iters) {
+    int lo = 0, hi = n + 1;  // lo qualifies, hi does not
+    while (hi - lo > 1) {
+        const int c = lo + (hi - lo) / 2;
+        if (update_num_iters(conf, (double)(n - c) / n, 4, max_iters) == max_iters) lo = c; else hi = c;
+    }
+    return lo;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2863,7 +2878,35 @@ __global__ __launch_bounds__(256) void ransac_tiles_kernel(RansacState* __restri
 // (it_off spacing), so no survivor is dropped; its order is the atomics' and does not matter.
 // A problem below kCapMinN points is left alone by stage 1, which marks its list length -1, and
 // stage 2's blocks then take its whole chunk in order: every iteration ends with a computed record.
-enum { kBoundUp = 0, kBoundLoUp = 1, kBoundCap = 2 };
+//
+// Strip form (kBoundStrip; a pre-stage of the cascade in the long-run schedule, maxIters > 4,096).  Dropping
+// the non-negative |ey| from the capped test leaves |ex| <= R with the same R per (tile, column block):
+// keep += clamp(R - |X'|), one MFMA and two VALU per pair.  Per pair the float value is >= the capped
+// form's ((R - |X'|) - |Y'| is that value less a non-negative term, and rounding is monotone), the sums run
+// in the same order, a zero row adds exactly 1 (R >= 1), so hi0 = floor(sum + slack) - padded rows >= hi1
+// >= hi >= the exact count.  The x coordinate: on C4's sets in the tiles' order the x strip keeps 54 points
+// of 2,000 for a hypothesis without a model and at most 151 over 184,000 of them, the y strip 71 and up to
+// 194, above the planted level of 160 (tools/bound_strip_sim.py, profiles/bound_strip_sim_c4.txt).
+// The strip launch writes every iteration's record, (0, hi0) for the countable ones, and lists nothing;
+// ransac_strip_pilot_kernel then sets a bar B per problem that a LATER iteration of the chunk justifies.
+//
+// The rule.  Let B be a level with
+//   (a) update_num_iters(conf, (n - (B + 1)) / n, 4, maxIters) == maxIters while niters still is maxIters:
+//       no best model with a count <= B shortens the loop (free_level below), and
+//   (b) some iteration u of the chunk, u < niters, has an exact count C_u > B (the pilot proves it with a
+//       lower bound of C_u: the prescreen's surely-in count).
+// Then every iteration t of the chunk with an upper bound hi_t <= B is recorded as not a candidate:
+//   u is reached: its count beats t's strictly, so t is never the final best, and by (a) t never changed
+//     niters (t's count <= B; niters was maxIters before, every earlier best of the chunk that changed it
+//     has a count > B and is kept);
+//   u is not reached: an earlier r ended the loop, by (a) only a count > B can, so hi_r >= its count > B:
+//     r is not dropped, is evaluated exactly as before, and beats t.
+// Ties: t is dropped only if hi_t <= B <= C_u - 1, so an iteration whose count equals the best one is
+// never dropped and "the first maximum wins" is untouched.
+// The problems where max(bar, B) leaves at most 1/16 of the chunk above it (the pilot's survivor list) keep
+// the strip records and go to stage 2 with that list; the others take the capped stage 1 as before
+// (kBoundCapRest: kBoundCap whose blocks return at once for a problem the strip settled).
+enum { kBoundUp = 0, kBoundLoUp = 1, kBoundCap = 2, kBoundStrip = 3, kBoundCapRest = 4 };
 
 template <int kMode, bool kList>
 __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const RansacState* __restrict__ st,
@@ -2876,9 +2919,11 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
                                                                 float thr2, int n_probs,
                                                                 const float4* __restrict__ tbox,
                                                                 int* __restrict__ surv, int* __restrict__ nsurv,
-                                                                int list_all) {
+                                                                int list_all, const int4* __restrict__ strip) {
     constexpr bool kLo = kMode == kBoundLoUp;
-    constexpr bool kCap = kMode == kBoundCap;
+    constexpr bool kCap = kMode == kBoundCap || kMode == kBoundCapRest;
+    constexpr bool kStrip = kMode == kBoundStrip;
+    constexpr bool kCapR = kCap || kStrip;  // R from the tile's |W| cap
     static_assert(!(kList && kMode != kBoundUp), "the survivor list takes the full upper form");
     __shared__ uint4 lt[2][kTileChunk * 128];
     // XCD-aware order: blocks b and b + 8 share an XCD under round-robin dispatch (speed only), so
@@ -2890,6 +2935,8 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
     const int tid = threadIdx.x, lane = tid & 63;
     const RansacState S = st[p];
     if (!S.active || S.done) return;  // uniform over the block
+    if (kStrip && S.n < kCapMinN) return;  // a small problem: the capped launch marks it
+    if (kMode == kBoundCapRest && strip[p].y) return;  // the strip records stand: listed by the pilot
     if (kCap && !list_all && S.n < kCapMinN) {  // a small problem: the full bound alone, from stage 2's grid
         if (kb == 0 && tid == 0) nsurv[p] = -1;
         return;
@@ -2997,12 +3044,12 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
     const h8v b1w = __builtin_bit_cast(h8v, lowh ? r3 : zero4);
     // in output units: K E + 1 (the band outside the upper test) and -K E_lo
     // (capped form: with the cap's own fp32 rounding, 2^-19 in the scaled units, under C)
-    const float EK = fmaf(kCap ? (E + C * 0x1p-19f) * (1.f + 1e-6f) : E, (float)kOutScale, 1.f);
+    const float EK = fmaf(kCapR ? (E + C * 0x1p-19f) * (1.f + 1e-6f) : E, (float)kOutScale, 1.f);
     const float ELK = -EL * (float)kOutScale;
     const float Cp = __shfl_xor(C, 32), Ep = __shfl_xor(EK, 32);
     // capped form: K (h6, h7, h8) of the two column blocks' hypotheses, as floats
     float wa0 = 0.f, wb0 = 0.f, wc0 = 0.f, wa1 = 0.f, wb1 = 0.f, wc1 = 0.f;
-    if (kCap) {
+    if (kCapR) {
         const float wa = count ? (float)h[6] * (float)kOutScale : 0.f;
         const float wb = count ? (float)h[7] * (float)kOutScale : 0.f;
         const float wc = count ? (float)h[8] * (float)kOutScale : 0.f;
@@ -3040,7 +3087,7 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
         const int tc = min(kTileChunk, nt - t0);
         if (t0 + kTileChunk < nt) stage(t0 + kTileChunk, buf ^ 1);
         if (wave_counts && MIM_PROBE_BOUND == 0) {
-          if (kCap) {  // |W'| capped over the tile's box: no W product
+          if (kCapR) {  // |W'| capped over the tile's box: no W product
             // the chunk's boxes (uniform: scalar loads) in one batch ahead of the tiles, so that no
             // tile waits for its own; the tile loop is unrolled to keep them in scalar registers
             float4 bx[kTileChunk];
@@ -3052,22 +3099,30 @@ __global__ __launch_bounds__(kBoundThreads) void ransac_bound_mfma_kernel(const 
                 asm volatile("" : "+s"(bx[t].x), "+s"(bx[t].y), "+s"(bx[t].z), "+s"(bx[t].w));
 #pragma unroll
             for (int t = 0; t < kTileChunk; ++t) {
+                // tiles past the chunk's last: the capped form leaves the loop; the strip form skips them one
+                // by one instead, because the compiler does not unroll its smaller body around a break, and the
+                // boxes' scalar registers (bx[t]) need the unrolled loop (a build that stops unrolling it fails
+                // to compile on the "+s" pins above: it cannot go unnoticed).  The strip form reads no ay: the
+                // y fragments are still staged into LDS with the x ones (the tiles interleave them, 128 uint4
+                // per tile, and the stage is one LDS-DMA run over the chunk), 16 KiB per stage it does not use
+                if (kStrip && t >= tc) continue;
                 if (t >= tc) break;
                 const h8v ax = __builtin_bit_cast(h8v, lt[buf][t * 128 + lane]);
                 const h8v ay = __builtin_bit_cast(h8v, lt[buf][t * 128 + 64 + lane]);
                 const f16acc zc = {};
                 const f16acc ex0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ax, b0x, zc, 0, 0, 0);
-                const f16acc ey0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b0y, zc, 0, 0, 0);
+                // (strip form: no y product)
+                const f16acc ey0 = kStrip ? zc : __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b0y, zc, 0, 0, 0);
                 const f16acc ex1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ax, b1x, zc, 0, 0, 0);
-                const f16acc ey1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b1y, zc, 0, 0, 0);
+                const f16acc ey1 = kStrip ? zc : __builtin_amdgcn_mfma_f32_32x32x16_f16(ay, b1y, zc, 0, 0, 0);
                 const float R0 = fmaf(C0, fmaf(fabsf(wa0), bx[t].z, fmaf(fabsf(wb0), bx[t].w,
                                           fabsf(fmaf(wa0, bx[t].x, fmaf(wb0, bx[t].y, wc0))))), E0);
                 const float R1 = fmaf(C1, fmaf(fabsf(wa1), bx[t].z, fmaf(fabsf(wb1), bx[t].w,
                                           fabsf(fmaf(wa1, bx[t].x, fmaf(wb1, bx[t].y, wc1))))), E1);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    keep0 += clamp01((R0 - fabsf(ex0[r])) - fabsf(ey0[r]));
-                    keep1 += clamp01((R1 - fabsf(ex1[r])) - fabsf(ey1[r]));
+                    keep0 += clamp01(kStrip ? R0 - fabsf(ex0[r]) : (R0 - fabsf(ex0[r])) - fabsf(ey0[r]));
+                    keep1 += clamp01(kStrip ? R1 - fabsf(ex1[r]) : (R1 - fabsf(ex1[r])) - fabsf(ey1[r]));
                 }
             }
           } else
@@ -3237,6 +3292,48 @@ __device__ __forceinline__ int wave_isum(int v) {
     return v;
 }
 
+// The prescreen's disc test of one sample's closed-form hypothesis (see above), shared with the strip pilot
+// (surely_in_count), whose lower bounds rest on the same "surely in": margins tt / tl, slack A, fp64.
+struct DiscTest {
+    double Hd[8], A, TT, TL;
+    // false: an invalid sample or one outside the conditioning screen (left to the exact kernel)
+    __device__ bool setup(const float4* __restrict__ P, int4 s4, const RansacState& S, float thr2) {
+        bool invalid = false, uncertain = false;
+        float eta = 0.f;
+        double eta_model = 0;
+        bound_hypothesis(P, s4, Hd, invalid, uncertain, eta, eta_model);
+        if (invalid || uncertain) return false;
+        float tt = thr2 + fmaf(1e-7f * S.smax, S.smax, 0.5f);
+        float tl = thr2 - fmaf(1e-7f * S.smax, S.smax, 0.5f);
+        if (eta > 0.f) {
+            const float wd = S.smax * fmaf(eta * eta, S.smax, 10.2f * eta);
+            tt += wd;
+            tl -= wd;
+        }
+        // |x|, |y| <= mx and |u|, |v| <= mu (powers of two from the tiles kernel's scales)
+        const double mx = ldexp(1.0, -ilogb((double)S.sa)), mu = ldexp(1.0, -ilogb((double)S.sb));
+        const double gam = 4.0 * 0x1p-24 + fmin(eta_model, 1.0);
+        const double ax = fmax((fabs(Hd[0]) + fabs(Hd[1])) * mx + fabs(Hd[2]),
+                               (fabs(Hd[3]) + fabs(Hd[4])) * mx + fabs(Hd[5]));
+        const double aw = (fabs(Hd[6]) + fabs(Hd[7])) * mx + 1.0;
+        A = gam * (ax + (mu + 6.0) * aw) * (1.0 + 1e-6);
+        TT = (double)tt * (1.0 + 1e-9);
+        TL = (double)fmaxf(tl, 0.f) * (1.0 - 1e-9);
+        return true;
+    }
+    __device__ __forceinline__ void point(const float4 q, bool& surely, bool& maybe) const {
+        const double x = q.x, y = q.y;
+        const double W = fma(Hd[6], x, fma(Hd[7], y, 1.0));
+        const double X = fma(Hd[0], x, fma(Hd[1], y, Hd[2]));
+        const double Y = fma(Hd[3], x, fma(Hd[4], y, Hd[5]));
+        const double ex = fabs(X - (double)q.z * W), ey = fabs(Y - (double)q.w * W);
+        const double ux = fmax(ex - A, 0.0), uy = fmax(ey - A, 0.0);
+        const double W2 = W * W;
+        maybe = ux * ux + uy * uy <= TT * W2;
+        surely = (ex + A) * (ex + A) + (ey + A) * (ey + A) < TL * W2;
+    }
+};
+
 constexpr int kPreWaves = 16;  // prescreen blocks (one wave each) per problem
 
 __global__ __launch_bounds__(64) void ransac_prescreen_kernel(const RansacState* __restrict__ st,
@@ -3267,39 +3364,12 @@ __global__ __launch_bounds__(64) void ransac_prescreen_kernel(const RansacState*
             cnt = bd.x;
         } else {
             const int4 s4 = decode_sample(samples[PD.it_off + t], stream, (unsigned)n, S.modM);
-            double Hd[8];
-            bool invalid = false, uncertain = false;
-            float eta = 0.f;
-            double eta_model = 0;
-            bound_hypothesis(P, s4, Hd, invalid, uncertain, eta, eta_model);
-            if (!invalid && !uncertain) {
-                float tt = thr2 + fmaf(1e-7f * S.smax, S.smax, 0.5f);
-                float tl = thr2 - fmaf(1e-7f * S.smax, S.smax, 0.5f);
-                if (eta > 0.f) {
-                    const float wd = S.smax * fmaf(eta * eta, S.smax, 10.2f * eta);
-                    tt += wd;
-                    tl -= wd;
-                }
-                // |x|, |y| <= mx and |u|, |v| <= mu (powers of two from the tiles kernel's scales)
-                const double mx = ldexp(1.0, -ilogb((double)S.sa)), mu = ldexp(1.0, -ilogb((double)S.sb));
-                const double gam = 4.0 * 0x1p-24 + fmin(eta_model, 1.0);
-                const double ax = fmax((fabs(Hd[0]) + fabs(Hd[1])) * mx + fabs(Hd[2]),
-                                       (fabs(Hd[3]) + fabs(Hd[4])) * mx + fabs(Hd[5]));
-                const double aw = (fabs(Hd[6]) + fabs(Hd[7])) * mx + 1.0;
-                const double A = gam * (ax + (mu + 6.0) * aw) * (1.0 + 1e-6);
-                const double TT = (double)tt * (1.0 + 1e-9), TL = (double)fmaxf(tl, 0.f) * (1.0 - 1e-9);
+            DiscTest D;
+            if (D.setup(P, s4, S, thr2)) {
                 int in = 0, unc = 0;
                 for (int i = lane; i < n; i += 64) {
-                    const float4 q = P[i];
-                    const double x = q.x, y = q.y;
-                    const double W = fma(Hd[6], x, fma(Hd[7], y, 1.0));
-                    const double X = fma(Hd[0], x, fma(Hd[1], y, Hd[2]));
-                    const double Y = fma(Hd[3], x, fma(Hd[4], y, Hd[5]));
-                    const double ex = fabs(X - (double)q.z * W), ey = fabs(Y - (double)q.w * W);
-                    const double ux = fmax(ex - A, 0.0), uy = fmax(ey - A, 0.0);
-                    const double W2 = W * W;
-                    const bool maybe = ux * ux + uy * uy <= TT * W2;
-                    const bool surely = (ex + A) * (ex + A) + (ey + A) * (ey + A) < TL * W2;
+                    bool surely, maybe;
+                    D.point(P[i], surely, maybe);
                     in += surely ? 1 : 0;
                     unc += (maybe && !surely) ? 1 : 0;
                 }
@@ -3445,7 +3515,7 @@ __global__ __launch_bounds__(kCandThreads) void ransac_cand_kernel(RansacState* 
                                                                    const ProbDev* __restrict__ probs,
                                                                    const int2* __restrict__ bounds, int c1,
                                                                    int* __restrict__ cand, int* __restrict__ ncand,
-                                                                   int L, int cap) {
+                                                                   int L, int cap, const int4* __restrict__ strip) {
     __shared__ int wred[kCandThreads / 64], wred2[kCandThreads / 64];
     const int p = blockIdx.x, tid = threadIdx.x;
     const RansacState S = st[p];
@@ -3471,7 +3541,10 @@ __global__ __launch_bounds__(kCandThreads) void ransac_cand_kernel(RansacState* 
     }
     const int init = max(3, max(S.max_good, S.lo_max));
     int all;
-    const int run0 = block_excl_max(lmax, init, wred, all);  // bound before this thread's first iteration
+    // bound before this thread's first iteration; with the strip pre-stage also its bar B, which a later
+    // iteration of the chunk justifies (ransac_bound_mfma_kernel, "The rule"): not a lower bound of
+    // maxGoodCount, so it stays out of lo_max
+    const int run0 = max(block_excl_max(lmax, init, wred, all), strip ? strip[p].x : 0);
     int cnt = 0, run = run0;
     for (int t = a; t < e; t += kB) {
         int2 v[kB];
@@ -3502,6 +3575,126 @@ __global__ __launch_bounds__(kCandThreads) void ransac_cand_kernel(RansacState* 
         // chunk 1's exact pass is never deferred into chunk 2's (measured -3 % on C3: the combined
         // pass has a longer Jacobi tail); the replay/exact kernels still accept a deferred list
         if (L == 0) st[p].defer = 0;
+    }
+}
+
+// Pilot of the strip pre-stage (ransac_bound_mfma_kernel, kBoundStrip): one block per problem, after the
+// strip launch has written (0, hi0) for the chunk.
+//  1. Each of the 16 waves takes the iteration with the largest hi0 among its own (t = c0 + thread, stride
+//     1,024; hi0 < n, so no uncertain record; the first on ties): 16 pilots, the chunk's largest hi0 among
+//     them.  On C4's sets every hypothesis of the planted model has a larger strip count (158 and more) than any
+//     of 184,000 without one (at most 151), so the largest is one of them wherever the chunk holds one
+//     (profiles/bound_strip_sim_c4.txt); sixteen cost a few microseconds and cover a chunk whose largest
+//     strip count belongs to a degenerate hypothesis.
+//  2. The wave counts the pilot's surely-in points with the prescreen's test (same closed-form hypothesis,
+//     fp64, same margins): a lower bound of its exact count, which is all condition (b) needs.  Invalid
+//     samples and those outside the conditioning screen count nothing.
+//  3. B = min(largest pilot count - 1, free_level - 1) while niters is still maxIters, else 0; bar =
+//     max(3, max_good, lo_max, B).
+//  4. The iterations with hi0 > bar are listed for stage 2.  The strip's records stand if they are at most
+//     1/16 of the chunk: a hypothesis without a model keeps 54 +- 20 points of C4's 2,000, so a bar the
+//     strip clears leaves a handful and one it does not (chunk 1's ~18) leaves most of the chunk; between
+//     the two the share decides directly what the margin would estimate, stage 2's work against the capped
+//     stage's (three MFMAs per listed pair against two per pair of the whole chunk).  Otherwise the list is
+//     dropped, B is not used and the capped stage takes the problem as before.
+// The pilot writes nsurv, surv and its own record only: no state the replay reads.
+constexpr int kPilotThreads = 1024;
+constexpr int kPilots = kPilotThreads / 64;
+constexpr int kStripListDiv = 16;
+
+// points surely inside the inner disc of the sample's closed-form hypothesis (ransac_prescreen_kernel's
+// test), summed over the wave; -1: invalid sample or outside the conditioning screen
+__device__ int surely_in_count(const float4* __restrict__ P, int n, int4 s4, const RansacState& S, float thr2) {
+    DiscTest D;
+    if (!D.setup(P, s4, S, thr2)) return -1;
+    int in = 0;
+    for (int i = (threadIdx.x & 63); i < n; i += 64) {
+        bool surely, maybe;
+        D.point(P[i], surely, maybe);
+        in += surely ? 1 : 0;
+    }
+    return wave_isum(in);
+}
+
+__global__ __launch_bounds__(kPilotThreads) void ransac_strip_pilot_kernel(const RansacState* __restrict__ st,
+                                                                           const ProbDev* __restrict__ probs,
+                                                                           const int2* __restrict__ bounds,
+                                                                           const float4* __restrict__ pts,
+                                                                           const int4* __restrict__ samples,
+                                                                           const uint32_t* __restrict__ stream,
+                                                                           int c0, int c1, float thr2, double conf,
+                                                                           int max_iters, int* __restrict__ surv,
+                                                                           int* __restrict__ nsurv,
+                                                                           int4* __restrict__ strip) {
+    __shared__ int wtop[kPilots];
+    __shared__ int s_bar, s_B, s_top, s_cnt;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const RansacState S = st[p];
+    if (!S.active || S.done || S.n < kCapMinN) {  // uniform over the block; a small problem: the capped launch marks it
+        if (tid == 0) strip[p] = make_int4(0, 0, 0, 0);
+        return;
+    }
+    const ProbDev PD = probs[p];
+    const int2* __restrict__ Bd = bounds + PD.it_off;
+    const int n = S.n;
+    const int t1 = min(min(c1, S.produced), S.niters);
+    unsigned long long key = 0;  // hi0 << 32 | ~t: the largest hi0, the first iteration on ties
+    for (int t = c0 + tid; t < t1; t += kPilotThreads) {
+        const int2 b = Bd[t];
+        if (b.x == 0 && b.y > 0 && b.y < n) {
+            const unsigned long long k = ((unsigned long long)(unsigned)b.y << 32) | (unsigned)~t;
+            key = k > key ? k : key;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned hi = __shfl_xor((unsigned)(key >> 32), off), lo = __shfl_xor((unsigned)key, off);
+        const unsigned long long k = ((unsigned long long)hi << 32) | lo;
+        key = k > key ? k : key;
+    }
+    int low = 0;
+    if (key) {  // uniform over the wave
+        const int t = (int)~(unsigned)key;
+        low = surely_in_count(pts + PD.good_off, n, decode_sample(samples[PD.it_off + t], stream, (unsigned)n, S.modM),
+                              S, thr2);
+    }
+    if (lane == 0) wtop[wv] = low;
+    __syncthreads();
+    if (tid == 0) {
+        int top = 0;
+        for (int w = 0; w < kPilots; ++w) top = max(top, wtop[w]);
+        int B = 0;
+        if (top > 1 && S.niters == max(max_iters, 1)) B = max(0, min(top, free_level(n, conf, S.niters)) - 1);
+        const int bar0 = max(3, max(S.max_good, S.lo_max));
+        s_B = B > bar0 ? B : 0;  // recorded only where it is the bar
+        s_top = top;
+        s_bar = max(bar0, B);
+        s_cnt = 0;
+    }
+    __syncthreads();
+    const int bar = s_bar, limit = (t1 - c0) / kStripListDiv;
+    int* __restrict__ SV = surv + PD.it_off;
+    for (int tb = c0; tb < t1; tb += kPilotThreads) {  // uniform trip count
+        const int t = tb + tid;
+        bool on = false;
+        if (t < t1) {
+            const int2 b = Bd[t];
+            on = b.x == 0 && b.y > bar;
+        }
+        const unsigned long long m = __ballot(on);
+        if (m) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&s_cnt, __popcll(m));
+            base = __shfl(base, 0);
+            const int pos = base + __popcll(m & ((1ull << lane) - 1));
+            if (on && pos < limit) SV[pos] = t;  // pos < limit <= the chunk: inside the problem's slice
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int cnt = s_cnt, stand = cnt <= limit ? 1 : 0;
+        nsurv[p] = stand ? cnt : 0;
+        strip[p] = make_int4(stand ? s_B : 0, stand, cnt, s_top);
     }
 }
 
@@ -4368,6 +4561,11 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
     const int bound_cap = (bce && bce[0] == '0') ? 0 : 1;
     const char* bae = getenv("MIM_BOUND_CAP_ALL");
     const int cap_all = (bae && bae[0] == '1') ? 1 : 0;
+    // strip pre-stage of the capped cascade in the long-run schedule (maxIters > 4,096: a first chunk of
+    // 4,096 and a long second one, where a later iteration is likely to set the bar and the two extra
+    // launches are small beside the chunk); MIM_BOUND_STRIP=0: the cascade alone
+    const char* bse = getenv("MIM_BOUND_STRIP");
+    const int strip = bound_cap && !cap_all && max_iters > 4096 && !(bse && bse[0] == '0');
     // the getSubset replay on the sampler stream when there is one (not in the reference mode)
     const bool split = b.s2 && !exact_all;
     hipStream_t ss = split ? b.s2 : s;
@@ -4498,21 +4696,52 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
             if (c0 == 0)
                 ransac_bound_mfma_kernel<kBoundLoUp, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
                     b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
-                    b.surv, b.nsurv, 0);
+                    b.surv, b.nsurv, 0, nullptr);
             else if (!bound_cap)
                 ransac_bound_mfma_kernel<kBoundUp, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
                     b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
-                    b.surv, b.nsurv, 0);
+                    b.surv, b.nsurv, 0, nullptr);
             else {
                 // stage 2's grid is fixed (the host does not know the counts): kSurvBlocks blocks per
                 // problem stride over its list; a block without entries ends after two loads
                 const int bppl = std::min(bppb, kSurvBlocks);
+                if (strip) {
+                    // strip pre-stage: every iteration's (0, hi0), the pilot's bar and list per problem,
+                    // then the capped stage for the problems the strip did not settle
+                    ransac_bound_mfma_kernel<kBoundStrip, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
+                        b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs,
+                        b.tbox, b.surv, b.nsurv, 0, nullptr);
+                    ransac_strip_pilot_kernel<<<n_probs, kPilotThreads, 0, s>>>(b.state, probs, b.bounds, pts, b.samples,
+                                                                               b.stream, c0, c1, thr2, prm.conf,
+                                                                               prm.max_iters, b.surv, b.nsurv, b.strip);
+                    ransac_bound_mfma_kernel<kBoundCapRest, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
+                        b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs,
+                        b.tbox, b.surv, b.nsurv, 0, b.strip);
+                    if (getenv("MIM_DEBUG_NSURV")) {
+                        std::vector<int4> h(n_probs);
+                        (void)hipMemcpyAsync(h.data(), b.strip, sizeof(int4) * n_probs, hipMemcpyDeviceToHost, s);
+                        (void)hipStreamSynchronize(s);
+                        int stand = 0, raised = 0; long long sum = 0, bsum = 0;
+                        for (int i = 0; i < n_probs; ++i) {
+                            stand += h[i].y;
+                            raised += h[i].x > 0;
+                            sum += h[i].y ? h[i].z : 0;
+                            bsum += h[i].x;
+                        }
+                        fprintf(stderr, "[mim] chunk [%d,%d): strip stands for %d of %d problems (listed mean %.1f), "
+                                "capped stage for %d; pilot bar on %d (mean %.1f)\n", c0, c1, stand, n_probs,
+                                stand ? (double)sum / stand : 0.0, n_probs - stand, raised, raised ? (double)bsum / raised : 0.0);
+                        if (n_probs == 1)
+                            fprintf(stderr, "[mim] chunk [%d,%d): problem 0: %d iterations above the bar, largest pilot count %d\n",
+                                    c0, c1, h[0].z, h[0].w);
+                    }
+                } else
                 ransac_bound_mfma_kernel<kBoundCap, false><<<8 * ((n_probs + 7) / 8) * bppb, kBoundThreads, 0, s>>>(
                     b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppb, thr2, n_probs, b.tbox,
-                    b.surv, b.nsurv, cap_all);
+                    b.surv, b.nsurv, cap_all, nullptr);
                 ransac_bound_mfma_kernel<kBoundUp, true><<<8 * ((n_probs + 7) / 8) * bppl, kBoundThreads, 0, s>>>(
                     b.state, probs, pts, b.samples, b.stream, b.tiles, b.bounds, c0, c1, bppl, thr2, n_probs, b.tbox,
-                    b.surv, b.nsurv, 0);
+                    b.surv, b.nsurv, 0, nullptr);
                 if (getenv("MIM_DEBUG_NSURV")) {
                     std::vector<int> h(n_probs);
                     (void)hipMemcpyAsync(h.data(), b.nsurv, sizeof(int) * n_probs, hipMemcpyDeviceToHost, s);
@@ -4545,7 +4774,9 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
             }
             const int L = c0 == 0 ? 0 : 1;  // candidate list of this chunk (at most two chunks)
             ransac_cand_kernel<<<n_probs, kCandThreads, 0, s>>>(b.state, probs, b.bounds, c1, b.cand, b.ncand, L,
-                                                                cap);
+                                                                cap, c0 > 0 && strip ? b.strip : nullptr);
+            // (the settle pass needs no B: every listed candidate has hi > B already, so max(its bar, B) drops
+            // nothing more)
             if (prescreen) {
                 ransac_prescreen_kernel<<<n_probs * kPreWaves, 64, 0, s>>>(b.state, probs, b.bounds, pts, b.samples,
                                                                           b.stream, b.cand, b.ncand, b.cex, b.cH,
@@ -4616,3 +4847,10 @@ void ransac_enqueue(const RansacParams& prm, int n_probs, const ProbDev* probs, 
 }
 
 }  // namespace mim
+
+// Test hook, not part of the API (include/mim.h does not declare it): free_level compiled for the host, for
+// tests/test_bound_strip_level.py.
+extern "C" int32_t mim_test_ransac_free_level(int32_t n, double confidence, int32_t max_iters) {
+    if (n < 1 || max_iters < 1) return 0;
+    return mim::free_level(n, confidence, max_iters);
+}
